@@ -9,7 +9,12 @@ utilisation sampler and its wall clock can see them), cycling over `--sets` dist
 set (0.5 GB per prompt at 8k) is never cache resident.  tokens/step = prompts * q_len * 32 layers.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2_w16|c2_w32|c2_w64|c3|c4|c5] [--tie-mode torch_cpu|canonical]
-                    [--mode batch|calls] [--in-flight 1..4]
+                    [--mode batch|calls] [--in-flight 1..4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, the path's algorithmic
+bytes).  --full adds what takes runs of its own: the live per-kernel breakdown behind the batch roofline, the extras
+(other tie and dot modes, prompts in flight, per-call paths, host path, N4 calls) and the CPU baseline with its parity
+counters.  --dump-outputs DIR writes what the last timed step handed its caller (K', V', kept indices) as DIR/<name>.npy.
 
 N > 1 (torchrun, one rank per GPU): the path shards by independent prompts/layers with no exchange, so every rank
 runs its own replica of the workload (weak scaling); time = max over ranks, value = N * tokens / time.
@@ -123,6 +128,34 @@ class Prompt:
         else:
             for p in self.plans:
                 p.run(p.handle)
+
+    def outputs(self):
+        """What one run hands its caller, per layer: K', V' and the kept indices."""
+        if self.mode == "batch":
+            return self.bp.k_out, self.bp.v_out, self.bp.idx
+        return [p.k_out for p in self.plans], [p.v_out for p in self.plans], [p.idx for p in self.plans]
+
+
+DUMP_BYTES = 60 << 20           # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(prompts, sets, out_dir):
+    """Writes the outputs the resident prompt sets `sets` hold (those the last timed step ran) as out_dir/set<s>_<name>.npy:
+    K' and V' (float32) and the kept indices (float64), each flattened over the layers in layer order.  DUMP_BYTES is split
+    evenly over the files; an array with more elements than its share holds is reduced to a fixed seeded sample of positions
+    (sorted, the same for every build), so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // (3 * len(sets))
+    for s in sets:
+        for j, (name, ts, dt) in enumerate(zip(("k_out", "v_out", "indices"), prompts[s].outputs(),
+                                               (torch.float32, torch.float32, torch.float64))):
+            flat = torch.cat([t.reshape(-1) for t in ts])
+            cap = share // dt.itemsize
+            if flat.numel() > cap:
+                pos = np.unique(np.random.default_rng(j).integers(0, flat.numel(), cap))
+                flat = flat[torch.from_numpy(pos).to(flat.device)]
+            np.save(os.path.join(out_dir, f"set{s}_{name}.npy"), flat.to(dt).cpu().numpy())
 
 
 def reduce_max_time(dt, dist, device):
@@ -352,8 +385,13 @@ def main():
     ap.add_argument("--streams", type=int, default=16, help="calls mode: HIP streams the 32 independent layer calls are spread over")
     ap.add_argument("--dot-mode", default="exact", choices=["exact", "mfma16"],
                     help="exact: f32-MFMA fmaf chain (bit-identical to the oracle); mfma16: packed bf16 MFMA scan (tolerance mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: per-kernel breakdown and batch roofline, extras, "
+                         "CPU baseline with parity counters")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (K', V', kept indices; sampled above 64 MB) as DIR/<name>.npy")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -387,6 +425,9 @@ def main():
     torch.cuda.synchronize(dev)
 
     dt, per = time_steps(prompts, per_step, a.steps, a.warmup, dev, dist, used)
+    if a.dump_outputs and rank == 0:        # before --full reruns prompts[0]; the sets follow time_steps' cycle
+        i_last = (a.warmup + a.steps - 1) * per_step
+        dump_outputs(prompts, sorted({(i_last + j) % n_sets for j in range(per_step)}), a.dump_outputs)
     tokens_per_step = per_step * cfg["L"] * LAYERS
     value = job_value(world, a.steps, tokens_per_step, dt)
     med_ms = statistics.median(per)
@@ -435,7 +476,7 @@ def main():
             if exact:
                 out["roofline"].update({"mfma_f32_TFLOPs": flops / t_layer / 1e12, "mfma_f32_peak_TFLOPs": MFMA_F32_PEAK_TFLOPS,
                                         "mfma_f32_frac": flops / t_layer / 1e12 / MFMA_F32_PEAK_TFLOPS})
-        elif a.mode == "batch":
+        elif a.mode == "batch" and a.full:     # the batch roofline rests on the live per-kernel breakdown
             kt = kernel_breakdown(prompts[0], dev, a.tie_mode)
             tot = sum(kt.values())
             out["kernels_us_per_32_layer_launch"] = {k_: round(v_ * 1e6, 1) for k_, v_ in kt.items()}
@@ -482,10 +523,10 @@ def main():
                                    "note": "latency-bound: one wave per head walks libstdc++'s heap / partition moves (a single dependent "
                                            "chain per head, DESIGN.md §3); its bytes are the pooled scores it reads and the indices it writes"}
             out["roofline"].update(kscan)
-        else:
+        elif a.mode == "calls":
             out["roofline"] = {"bound": "hbm", "kernel": "whole per-call path (latency-bound launches)", "achieved": path_b / t_layer / 1e9,
                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": path_b / t_layer / 1e9 / HBM_PEAK_GBS, "traffic": None}
-        if not a.no_extras and world == 1 and not h2o:
+        if a.full and not a.no_extras and world == 1 and not h2o:
             extra = {}
             half = max(5, a.steps // 5)
 
@@ -592,7 +633,7 @@ def main():
             except Exception as e:
                 extra["n4_error"] = repr(e)
             out["extras"] = extra
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, dev=dev)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -15,7 +15,7 @@ stats() {   # stats <name> <prof_driver args...>: per-kernel averages of the com
   echo "== $name"; cat $OUT/${TAG}_kernel_stats_$name.csv
 }
 # 1. the default bench command under the profiler (its own summary line is kept too)
-rm -rf /tmp/kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_under_rocprof.log 2>&1
+rm -rf /tmp/kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras > $OUT/${TAG}_bench_under_rocprof.log 2>&1
 grep "kvc::\|^\"Name" /tmp/kt/*/*_kernel_stats.csv > $OUT/${TAG}_kernel_stats_c2_bench_command.csv
 # 2. the batched launches alone, per configuration (average = one 32-layer launch)
 stats c2_batch_launches_only c2 torch_cpu 10 batch
@@ -44,5 +44,5 @@ head -25 /tmp/kt_n2/*/*_kernel_stats.csv > $OUT/${TAG}_n2_kernel_stats.csv
 # 5. round 3: the matrix-core probes behind h2o_fused_kernel (16x16x4 f32 accumulation order; sustained f32 MFMA rate), its phase shares
 (cd $R/tools && for p in mfma16x4_probe mfma_peak_probe; do [ -x ./$p ] && ./$p > $OUT/${TAG}_$p.txt 2>&1; done)
 [ -f $R/tools/diag/libkvc_hip_stamps.so ] && KVC_LIB_PATH=$R/tools/diag/libkvc_hip_stamps.so python3 $R/tools/h2o_fused_stamps.py > $OUT/${TAG}_h2o_fused_stamps.txt 2>&1
-(cd $R && python3 bench.py --config c3 --steps 5 --warmup 2 > $OUT/${TAG}_bench_c3_exact.json 2> /dev/null; python3 bench.py --steps 30 --warmup 5 > $OUT/${TAG}_bench_c2.json 2> /dev/null)
+(cd $R && python3 bench.py --config c3 --steps 5 --warmup 2 --full > $OUT/${TAG}_bench_c3_exact.json 2> /dev/null; python3 bench.py --steps 30 --warmup 5 --full > $OUT/${TAG}_bench_c2.json 2> /dev/null)
 ls -la $OUT
