@@ -107,7 +107,10 @@ typedef struct kvc_params {
                                   Bit11 (H2O exact mode, testing): round 2's kernels that write the logit matrix to the
                                   workspace instead of the fused one that keeps 16 query rows of it in registers (identical results).
                                   Bit12 (measurement): at windows 16 / 32 / 64 the one-workgroup-per-head softmax stage that reads the
-                                  logits twice instead of the 16-rows-per-workgroup form that reads them once (identical results). */
+                                  logits twice instead of the 16-rows-per-workgroup form that reads them once (identical results).
+                                  Bit13 (testing): tie_mode torch_cpu with every budget in the one-wave heap's regime (16-bit,
+                                  1 <= k <= 128, k * 64 <= q_len - window): the separate selection and gather launches instead of
+                                  the kernel that copies K / V rows as the selection finalises them (identical results). */
     int32_t dot_mode;          /* kvc_dot_mode */
     int64_t q_stride_b, q_stride_h, q_stride_l;   /* element strides of q[b][h][l][:] */
     int64_t k_stride_b, k_stride_h, k_stride_l;

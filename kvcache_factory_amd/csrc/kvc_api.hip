@@ -246,6 +246,11 @@ int enqueue_select(const kvc_params* p, const Items& it, bool fuse, void* exact_
     if (fuse) { s.fuse = 1; s.gk = gather_args(p, it, 0, true); s.gv = gather_args(p, it, 1, true); }
     s.members_only = members_only ? 1 : 0;
     if (p->tie_mode == KVC_TIES_TORCH_CPU) {
+        if (fuse) {                                          // the caller checked kvc::select_gather_eligible
+            const int rc = kvc::launch_select_gather(s, p->dtype, st);
+            if (rc) return fail(rc, "exact select + gather launch failed");
+            return hip_ok("exact select + gather launch");
+        }
 #if defined(KVC_STAMPS)
         if (p->debug_stage_mask & 32) s.fuse = 2;            // diag build: phase stamps over the index output (no gather follows)
 #endif
@@ -342,7 +347,14 @@ int run_items(const kvc_params* p, Items& it, void* workspace, size_t workspace_
         const kvc::GatherArgs gk = gather_args(p, it, 0, false), gv = gather_args(p, it, 1, false);
         return enqueue_gather(&gk, &gv, st);
     }
-    const bool fuse = it.k_max <= kvc::kFuseGatherMaxK && p->tie_mode == KVC_TIES_CANONICAL;
+    // the gather rides in the selecting kernel: canonical ties up to kFuseGatherMaxK; torch_cpu ties when every item takes
+    // WaveHeapL (debug_stage_mask bit 13: the separate select_exact + gather launches instead, identical results)
+    bool fuse = it.k_max <= kvc::kFuseGatherMaxK && p->tie_mode == KVC_TIES_CANONICAL;
+    if (p->tie_mode == KVC_TIES_TORCH_CPU && !(dbg & 8192))
+        fuse = kvc::select_gather_eligible(p->dtype, p->q_len - p->window, p->head_dim * es, it.keep, it.n);
+#if defined(KVC_STAMPS)
+    if (dbg & 32) fuse = fuse && p->tie_mode == KVC_TIES_CANONICAL;     // stamps in the index output: the separate select_exact
+#endif
     if (int rc = enqueue_select(p, it, fuse, ws + l.total * (size_t)it.n, st)) return rc;
     if (fuse) return KVC_OK;
 #if defined(KVC_STAMPS)

@@ -186,6 +186,8 @@ int launch_select(const SelectArgs& a, int dtype, int tie_mode, hipStream_t st);
 size_t select_lds_bytes(int k);
 int launch_select_exact(const SelectArgs& a, int dtype, void* scratch, hipStream_t st);   // tie_mode torch_cpu
 size_t select_exact_scratch_bytes(int heads, int n, int k);     // per item
+bool select_gather_eligible(int dtype, int n, int row_bytes, const int* keep, int n_items);   // tie_mode torch_cpu, WaveHeapL budgets
+int launch_select_gather(const SelectArgs& a, int dtype, hipStream_t st);                     // select_exact + gather in one kernel (gk, gv)
 int launch_gather(const GatherPair& p, hipStream_t st);
 struct CamArgs {           // CAM (kvc_cam.hip)
     const void* logits; const float* rowmax; const float* rowsum;      // the scoring stage's workspace regions

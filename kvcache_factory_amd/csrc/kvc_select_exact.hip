@@ -237,6 +237,15 @@ __device__ __forceinline__ uint32_t vsel(uint32_t a, uint32_t b, u64 mask) {    
     asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(mask));
     return d;
 }
+// The heap's hand-offs between lanes through LDS.  SOLO: the wave is its workgroup (select_exact_kernel), s_barrier as
+// everywhere.  Otherwise (select_gather_kernel) the other wave of the workgroup does not follow the heap's control flow and
+// must never meet a barrier: one wave's LDS operations execute in issue order, so waiting for its own and keeping the
+// compiler from moving LDS accesses across the point is the whole hand-off.
+template <bool SOLO>
+__device__ __forceinline__ void heap_sync() {
+    if constexpr (SOLO) __syncthreads();
+    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
 struct WaveHeapL {
     typedef HeapNode<uint32_t> N;
     static constexpr uint32_t SENT = 0xffffffffu;
@@ -376,6 +385,7 @@ struct WaveHeapL {
 #undef KVC_HEAPL_BLOCK_A
 #undef KVC_HEAPL_MOVES
     // lo_init / hi_init: nodes lane, lane + 64 (SENT beyond the length)
+    template <bool SOLO = true>
     __device__ __forceinline__ void init(uint32_t* lds, uint32_t lo_init, uint32_t hi_init) {
         lane = threadIdx.x;
         lvl = 31 - __clz(lane + 1);
@@ -389,9 +399,9 @@ struct WaveHeapL {
         for (int c = lane; c > 0;) { const int p = (c - 1) >> 1; A |= 1u << p; if (c & 1) R |= 1u << p; c = p; }
         lo = lo_init;
         lds[lane] = lo_init; lds[lane + 64] = hi_init; lds[lane + 128] = SENT;
-        __syncthreads();
+        heap_sync<SOLO>();
         xl = lds[2 * lane + 1]; xr = lds[2 * lane + 2];
-        __syncthreads();
+        heap_sync<SOLO>();
         lds[lane + 64] = SENT;
         refresh();
     }
@@ -471,8 +481,12 @@ __device__ __forceinline__ uint32_t keys16x2(uint32_t x) {                     /
 __device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
 }
-template <int DT>
-__device__ __forceinline__ void partial_sort_waveL(const typename Dt<DT>::raw* s, int n_, int k_, uint32_t* lds, int64_t* out) {
+// SOLO = false (select_gather_kernel): the wave shares its workgroup with a copy wave and publishes, after each pop of
+// __sort_heap, the lowest result position that is final in *done (LDS; positions >= *done hold their final node in res).
+typedef __attribute__((address_space(3))) volatile uint32_t lds_vu32;
+template <int DT, bool SOLO = true>
+__device__ __forceinline__ void partial_sort_waveL(const typename Dt<DT>::raw* s, int n_, int k_, uint32_t* lds, int64_t* out,
+                                                   uint32_t* done = nullptr) {
     static_assert(Key<DT>::bits == 16, "packed 32-bit nodes");
     typedef HeapNode<uint32_t> N;
     const int lane = threadIdx.x;
@@ -500,9 +514,9 @@ __device__ __forceinline__ void partial_sort_waveL(const typename Dt<DT>::raw* s
     request(0);
     KVC_HSTAMP(0);
     land(0);                                                                    // keys 0 .. 511 - e0: the heap's k <= 128
-    __syncthreads();
+    heap_sync<SOLO>();
     WaveHeapL H;
-    H.init(lds, lane < k ? N::make(seg[e0 + lane], lane) : WaveHeapL::SENT,
+    H.template init<SOLO>(lds, lane < k ? N::make(seg[e0 + lane], lane) : WaveHeapL::SENT,
            lane + 64 < k ? N::make(seg[e0 + lane + 64], lane + 64) : WaveHeapL::SENT);
     KVC_HSTAMP(1);
     H.make_heap(k);
@@ -515,7 +529,7 @@ __device__ __forceinline__ void partial_sort_waveL(const typename Dt<DT>::raw* s
     constexpr int U = 8;
     for (int g = 0; g * kSegKeys < total; ++g) {
         const bool more = (g + 1) * kSegKeys < total;
-        __syncthreads();
+        heap_sync<SOLO>();
         if (more) request(g + 1);
         for (int jb = 0; jb < kSegKeys; jb += U * 64) {
             const int ib = g * kSegKeys + jb - e0;                               // row element of the batch's first key
@@ -551,7 +565,7 @@ __device__ __forceinline__ void partial_sort_waveL(const typename Dt<DT>::raw* s
             }
         }
         if (more) {
-            __syncthreads();
+            heap_sync<SOLO>();
 #pragma unroll
             for (int u = 0; u < VPL; ++u) land(u);
         }
@@ -566,14 +580,19 @@ __device__ __forceinline__ void partial_sort_waveL(const typename Dt<DT>::raw* s
         res[last] = top;
         H.remove(last);
         H.refresh();
-        for (int l = last; l >= 1; --l) value = H.pop_step(value, l - 1, res);      // (the last one stores res[0])
+        if constexpr (!SOLO) { asm volatile("" ::: "memory"); *(lds_vu32*)done = (uint32_t)last; }
+        for (int l = last; l >= 1; --l) {
+            value = H.pop_step(value, l - 1, res);                               // (the last one stores res[0])
+            if constexpr (!SOLO) { asm volatile("" ::: "memory"); *(lds_vu32*)done = (uint32_t)(l - 1); }   // res[l - 1] is final
+        }
     } else {
         res[0] = H.lo;                                                           // k == 1: lane 0's node; every lane writes, lane 63 last
         asm volatile("" ::: "memory");
         if (lane == 0) res[0] = H.lo;
     }
+    if constexpr (!SOLO) { asm volatile("" ::: "memory"); *(lds_vu32*)done = 0u; }
     KVC_HSTAMP(4);
-    __syncthreads();
+    heap_sync<SOLO>();
     if (lane < k) out[lane] = N::index(res[lane]);
     if (lane + 64 < k) out[lane + 64] = N::index(res[lane + 64]);
     KVC_HSTAMP(5);
@@ -1504,6 +1523,81 @@ __global__ __launch_bounds__(64) void select_exact_kernel(const SelectArgs a, u6
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// select_gather_kernel: select_exact_kernel's WaveHeapL path (partial_sort, 1 <= k <= 128, 16-bit, n <= 65536) and
+// gather_kernel's copy of the head's k + W rows of K and V, in one workgroup of two waves.  Wave 0 runs the heap exactly as
+// select_exact_kernel does; wave 1 copies the W window-tail rows (they do not depend on the selection) while the heap
+// runs, then follows __sort_heap: every pop makes one result position final (k - 1 first), the heap wave publishes the
+// lowest final position in LDS, and the copy wave moves the rows of the positions it has not moved yet.  What is left
+// after the last pop is one batch of row copies instead of a launch of its own behind the slowest head.
+// Past the one barrier at entry the waves meet only through LDS words (the heap wave's hand-offs are heap_sync<false>).
+// grid = (heads, items), block = 128.  LDS: kSelectGatherLds.
+// ---------------------------------------------------------------------------------------------------------
+constexpr size_t kSelectGatherLds = kWaveHeapLLds + 16;            // heap exchange area + one segment of keys, `done`
+template <int DT>
+__global__ __launch_bounds__(128) void select_gather_kernel(const SelectArgs a) {
+    typedef typename Dt<DT>::raw raw;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint32_t* const lds = reinterpret_cast<uint32_t*>(smem);
+    uint32_t* const done = lds + kWaveHeapLLds / 4;
+    const int head = blockIdx.x, item = blockIdx.y;
+    const int n = uni(a.n), k = uni(a.k.v[item]);
+    if (threadIdx.x == 0) *(lds_vu32*)done = (uint32_t)k;              // nothing final yet
+    __syncthreads();                                                   // the only barrier: the waves part here
+    if (threadIdx.x < 64) {
+        const raw* s = reinterpret_cast<const raw*>((uintptr_t)uni((u64)reinterpret_cast<uintptr_t>(a.scores.p[item]))) + (int64_t)head * n;
+        int64_t* out = reinterpret_cast<int64_t*>((uintptr_t)uni((u64)reinterpret_cast<uintptr_t>(a.idx.p[item]))) + (int64_t)head * k;
+        partial_sort_waveL<DT, false>(s, n, k, lds, out, done);
+        return;
+    }
+    // the copy wave: lane = (row r of the rows_per_op moved by one instruction, 16-byte piece c of that row)
+    const int lane = threadIdx.x - 64;
+    const int cpr = a.gk.row_bytes >> 4, rpo = 64 / cpr;               // pieces per row (a divisor of 64: launcher), rows per op
+    const int r = lane / cpr, c = lane - r * cpr;
+    const int hq = a.gk.n_q_heads, b = head / hq, kvh = (head % hq) / a.gk.group;
+    const int W = a.gk.window, cap = k + W;
+    const int64_t es = a.gk.esize;
+    const char* const ks = reinterpret_cast<const char*>((uintptr_t)uni((u64)reinterpret_cast<uintptr_t>(a.gk.src.p[item]))) +
+                           ((int64_t)b * a.gk.stride_b + (int64_t)kvh * a.gk.stride_h) * es + c * 16;
+    const char* const vs = reinterpret_cast<const char*>((uintptr_t)uni((u64)reinterpret_cast<uintptr_t>(a.gv.src.p[item]))) +
+                           ((int64_t)b * a.gv.stride_b + (int64_t)kvh * a.gv.stride_h) * es + c * 16;
+    const int64_t ksl = a.gk.stride_l * es, vsl = a.gv.stride_l * es;
+    const int64_t kob = uni((u64)a.gk.out_head_bytes.v[item]), vob = uni((u64)a.gv.out_head_bytes.v[item]);
+    const int64_t rb = a.gk.row_bytes;
+    char* const ko = reinterpret_cast<char*>((uintptr_t)uni((u64)reinterpret_cast<uintptr_t>(a.gk.out.p[item]))) +
+                     (int64_t)head * (kob ? kob : cap * rb) + c * 16;
+    char* const vo = reinterpret_cast<char*>((uintptr_t)uni((u64)reinterpret_cast<uintptr_t>(a.gv.out.p[item]))) +
+                     (int64_t)head * (vob ? vob : cap * rb) + c * 16;
+    const lds_vu32* const res = (const lds_vu32*)(lds + 192);
+    // output rows [t0, t1): source row srow(t); four ops of rows in flight per batch (a lane past t1 loads row t1 - 1 again
+    // and stores nothing: straight-line code, the rows in registers)
+    auto copy = [&](int t0, int t1, auto srow) {
+        for (int t = t0 + r; t < t1 + r; t += 4 * rpo) {
+            const int t1c = t + rpo, t2 = t + 2 * rpo, t3 = t + 3 * rpo, last = t1 - 1;
+            const int64_t s0 = srow(t < t1 ? t : last), s1 = srow(t1c < t1 ? t1c : last);
+            const int64_t s2 = srow(t2 < t1 ? t2 : last), s3 = srow(t3 < t1 ? t3 : last);
+            const uint4 k0 = *reinterpret_cast<const uint4*>(ks + s0 * ksl), v0 = *reinterpret_cast<const uint4*>(vs + s0 * vsl);
+            const uint4 k1 = *reinterpret_cast<const uint4*>(ks + s1 * ksl), v1 = *reinterpret_cast<const uint4*>(vs + s1 * vsl);
+            const uint4 k2 = *reinterpret_cast<const uint4*>(ks + s2 * ksl), v2 = *reinterpret_cast<const uint4*>(vs + s2 * vsl);
+            const uint4 k3 = *reinterpret_cast<const uint4*>(ks + s3 * ksl), v3 = *reinterpret_cast<const uint4*>(vs + s3 * vsl);
+            if (t < t1) { *reinterpret_cast<uint4*>(ko + (int64_t)t * rb) = k0; *reinterpret_cast<uint4*>(vo + (int64_t)t * rb) = v0; }
+            if (t1c < t1) { *reinterpret_cast<uint4*>(ko + (int64_t)t1c * rb) = k1; *reinterpret_cast<uint4*>(vo + (int64_t)t1c * rb) = v1; }
+            if (t2 < t1) { *reinterpret_cast<uint4*>(ko + (int64_t)t2 * rb) = k2; *reinterpret_cast<uint4*>(vo + (int64_t)t2 * rb) = v2; }
+            if (t3 < t1) { *reinterpret_cast<uint4*>(ko + (int64_t)t3 * rb) = k3; *reinterpret_cast<uint4*>(vo + (int64_t)t3 * rb) = v3; }
+        }
+    };
+    copy(k, cap, [&](int t) { return (int64_t)n + (t - k); });         // the window tail: rows q_len - W .. q_len - 1
+    // then the selected rows, as the pops make their positions final.  The heap wave always ends by publishing 0; the
+    // bound on the polls (about a second of sleeping) only keeps a wave that never gets there from holding the GPU.
+    int hi = k;
+    for (int polls = 0; hi > 0 && polls < (1 << 23);) {
+        const int d = __builtin_amdgcn_readfirstlane((int)*(const lds_vu32*)done);
+        if (d >= hi) { __builtin_amdgcn_s_sleep(2); ++polls; continue; }
+        copy(d, hi, [&](int t) { return (int64_t)(res[t] & 0xffffu); });
+        hi = d;
+    }
+}
+
 // LDS list region behind `fixed` bytes of a workgroup: what the lists of an n-element range need, cut back to what keeps
 // as many workgroups resident per CU as the minimal region would (160 KB per CU, counted in 1280-byte granules).
 static size_t list_region_bytes(size_t fixed, int n) {
@@ -1624,6 +1718,24 @@ int launch_sort_prefix(const RaggedSortArgs& a, int dtype, void* scratch, hipStr
         case KVC_BF16: return launch_sort_prefix_t<KVC_BF16>(a, scratch, st);
         case KVC_FP16: return launch_sort_prefix_t<KVC_FP16>(a, scratch, st);
         case KVC_FP32: return launch_sort_prefix_t<KVC_FP32>(a, scratch, st);
+    }
+    return KVC_ERR_INVALID;
+}
+
+// select_gather_kernel serves a launch when every item takes WaveHeapL (16-bit, n <= 65536, 1 <= k <= 128, k * 64 <= n)
+// and a row is a whole number of 16-byte pieces that divides 64 lanes.
+bool select_gather_eligible(int dtype, int n, int row_bytes, const int* keep, int n_items) {
+    if ((dtype != KVC_BF16 && dtype != KVC_FP16) || n > 65536 || row_bytes < 16 || row_bytes % 16 || 64 % (row_bytes / 16)) return false;
+    for (int i = 0; i < n_items; ++i)
+        if (keep[i] < 1 || keep[i] > kWaveHeapMaxK || (int64_t)keep[i] * 64 > (int64_t)n) return false;
+    return true;
+}
+
+int launch_select_gather(const SelectArgs& a, int dtype, hipStream_t st) {
+    const dim3 g((unsigned)a.heads, (unsigned)a.n_items);
+    switch (dtype) {
+        case KVC_BF16: hipLaunchKernelGGL((select_gather_kernel<KVC_BF16>), g, dim3(128), kSelectGatherLds, st, a); return 0;
+        case KVC_FP16: hipLaunchKernelGGL((select_gather_kernel<KVC_FP16>), g, dim3(128), kSelectGatherLds, st, a); return 0;
     }
     return KVC_ERR_INVALID;
 }
