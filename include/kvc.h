@@ -234,6 +234,77 @@ int kvc_decode_step2(const kvc_decode_params* p, const kvc_decode_ext* ext /* nu
                      const void* k_pruned /* nullable */, const int16_t* chan /* nullable */, void* out,
                      void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
 
+/* ---- quantized decode cache (KIVI-style, --quant_method kivi --nbits N of the reference's run scripts) ----------------------
+ * Rule: asymmetric round-to-nearest, every group on its own in fp32 with the inputs widened exactly.  KEYS are grouped per
+ * channel (G = group_size consecutive stored rows share one (scale, zero) per channel; a segment whose rows are not a multiple
+ * of G ends with a partial group that gets its own min / max); VALUES are grouped per token (G consecutive channels of one row
+ * share one (scale, zero)).  With qmax = 2^nbits - 1 and mn, mx the group's minimum and maximum:
+ *     scale = (mx - mn) / qmax                                          fp32, correctly rounded division
+ *     code  = scale > 0 ? clamp(rint((x - mn) / scale), 0, qmax) : 0     rint = round half to even
+ *     x'    = fmaf(code, scale, mn)                                      the de-quantized value
+ * (the library is built with -ffp-contract=off and correctly rounded fp32 division, so codes, scales and zeros are
+ * reproducible bit for bit by any fp32 restatement).  Inputs are assumed finite: a NaN or an infinity in a group gives
+ * unspecified codes for that group.  nbits 2, 4 or 8; G 32, 64 or 128 dividing head_dim; head_dim 64 or 128; bf16 / fp16 / fp32.
+ *
+ * Layout of one segment of `capacity` rows per head (b, h) — the same for the prompt, the quantized tail, keys and values:
+ *   codes  [b][h][capacity][head_dim * nbits / 8] bytes, rows dense: channel d of a row sits at bit d * nbits of the row,
+ *          little-endian within each byte (channel 0 in the low bits of byte 0);
+ *   key metadata   [b][h][ceil(capacity / G)][2][head_dim] fp32: per group the scale of every channel, then the zero (= mn)
+ *                  of every channel;
+ *   value metadata [b][h][capacity][head_dim / G][2] fp32: per row and channel group the pair (scale, zero).
+ * Code strides are in bytes (multiples of 16), metadata strides in floats (key: multiples of 4, value: of 2), source /
+ * destination strides in elements. */
+typedef enum kvc_quant_mode { KVC_QUANT_KEYS = 0, KVC_QUANT_VALUES = 1 } kvc_quant_mode;
+
+typedef struct kvc_quant_params {      /* kvc_quantize_rows / kvc_dequantize_rows: rows [row0, row0 + rows) of one segment */
+    int32_t dtype, bsz, n_heads, head_dim;
+    int32_t nbits, group_size;
+    int32_t mode;                      /* kvc_quant_mode */
+    int32_t row0;                      /* first segment row written / read (keys: a multiple of group_size) */
+    int32_t rows;                      /* rows quantized / de-quantized (0: nothing to do) */
+    int32_t capacity;                  /* rows per head the code and metadata buffers hold */
+    int64_t src_stride_b, src_stride_h, src_stride_l;       /* elements: the [b][h][row][d] source (quantize) or destination */
+    int64_t code_stride_b, code_stride_h;                   /* bytes */
+    int64_t meta_stride_b, meta_stride_h;                   /* floats */
+} kvc_quant_params;
+
+/* quantize: src rows [0, rows) -> segment rows [row0, row0 + rows) (codes and this mode's metadata; key groups start at row0).
+ * dequantize: segment rows [row0, row0 + rows) -> dst rows [0, rows) in dtype (x' rounded to dtype). */
+int kvc_quantize_rows(const kvc_quant_params* p, const void* src, uint8_t* codes, float* meta, void* hip_stream);
+int kvc_dequantize_rows(const kvc_quant_params* p, const uint8_t* codes, const float* meta, void* dst, void* hip_stream);
+
+typedef struct kvc_quant_seg {         /* one quantized segment of the decode cache (layout above) */
+    const uint8_t* k_codes; const uint8_t* v_codes;
+    const float* k_meta; const float* v_meta;
+    int32_t rows, capacity;            /* rows in use / rows per head the buffers hold */
+    int64_t code_stride_b, code_stride_h;                   /* bytes, k_codes and v_codes alike */
+    int64_t k_meta_stride_b, k_meta_stride_h, v_meta_stride_b, v_meta_stride_h;     /* floats */
+} kvc_quant_seg;
+
+/* kvc_decode_step_quant: kvc_decode_step2 over a quantized cache of four segments, one attention per (query head, new token):
+ *   prefix [b][H_q]   the compressed prompt quantized once (rows = k + W);
+ *   qtail  [b][H_kv]  decoded rows quantized in whole key groups, append-only (rows a multiple of G);
+ *   residual k_res / v_res [b][H_kv][res_capacity][head_dim] in dtype: res_rows full-precision rows;
+ *   the step's new_rows K / V rows, which the call appends to the residual at row res_rows (as kvc_decode_step does to its tail).
+ * Token i sees the prefix, the quantized tail and residual rows [0, res_rows + i + 1).  The attention runs over the
+ * de-quantized values x' (above) with fp32 accumulation; output [b][h_q][i][:] in dtype.  Moving residual rows onto the
+ * quantized tail (kvc_quantize_rows) is the caller's business: res_rows < residual_length on entry, residual_length a positive
+ * multiple of G.  Workspace: kvc_decode_quant_workspace_bytes(p) (less, or NULL, only reduces the number of splits). */
+typedef struct kvc_decode_quant_params {
+    int32_t dtype, bsz, n_q_heads, n_kv_heads, head_dim;
+    int32_t nbits, group_size, residual_length;
+    int32_t res_rows, res_capacity, new_rows;
+    float scaling;
+    int64_t q_stride_b, q_stride_h, q_stride_l;             /* q[b][h_q][i][:] */
+    int64_t new_stride_b, new_stride_h, new_stride_l;       /* k_new / v_new [b][h_kv][i][:] */
+    int64_t res_stride_b, res_stride_h;                     /* k_res / v_res [b][h_kv][row][:], rows dense */
+    int64_t out_stride_b, out_stride_h, out_stride_l;       /* out[b][h_q][i][:] */
+} kvc_decode_quant_params;
+size_t kvc_decode_quant_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail);
+int kvc_decode_step_quant(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail,
+                          const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
+                          void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
+
 /* ---- AdaKV / HeadKV: per-head budgets, ragged ("flattened") cache -----------------------------------
  * Replaces AdaKVCluster.update_kv (pyramidkv_utils.py:674-757), HeadKVCluster.update_kv (:813-878) and, at decode, the
  * repo's native update_flatten_view (csrc/csrc/cuda_api.cu:12-85) + flash_attn_varlen_func (llama_model.py:2363-2390).

@@ -27,7 +27,8 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_select_workspace_bytes", "kvc_decode_step", "kvc_ragged_workspace_bytes", "kvc_ragged_plan",
            "kvc_ragged_compact", "kvc_ragged_decode_step", "kvc_l2norm_workspace_bytes", "kvc_l2norm_compress",
            "kvc_merge_workspace_bytes", "kvc_merge_pivot", "kvc_think_prune", "kvc_decode_workspace_bytes", "kvc_decode_step2",
-           "kvc_cam_workspace_bytes", "kvc_cam_plan", "kvc_cam_merge")
+           "kvc_cam_workspace_bytes", "kvc_cam_plan", "kvc_cam_merge", "kvc_quantize_rows", "kvc_dequantize_rows",
+           "kvc_decode_quant_workspace_bytes", "kvc_decode_step_quant")
 
 
 class KvcError(RuntimeError):
@@ -69,6 +70,27 @@ class DecodeExt(ctypes.Structure):
     _fields_ = [("v_prefix_stride_b", ctypes.c_int64), ("v_prefix_stride_h", ctypes.c_int64), ("pruned_rows", ctypes.c_int32),
                 ("pruned_dim", ctypes.c_int32), ("pruned_stride_b", ctypes.c_int64), ("pruned_stride_h", ctypes.c_int64),
                 ("chan_stride_b", ctypes.c_int64), ("chan_stride_h", ctypes.c_int64)]
+
+
+class QuantParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("dtype", "bsz", "n_heads", "head_dim", "nbits", "group_size", "mode", "row0", "rows",
+                                               "capacity")] + [
+        (n, ctypes.c_int64) for n in ("src_stride_b", "src_stride_h", "src_stride_l", "code_stride_b", "code_stride_h",
+                                      "meta_stride_b", "meta_stride_h")]
+
+
+class QuantSeg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("k_codes", "v_codes", "k_meta", "v_meta")] + [
+        ("rows", ctypes.c_int32), ("capacity", ctypes.c_int32)] + [
+        (n, ctypes.c_int64) for n in ("code_stride_b", "code_stride_h", "k_meta_stride_b", "k_meta_stride_h", "v_meta_stride_b",
+                                      "v_meta_stride_h")]
+
+
+class DecodeQuantParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("dtype", "bsz", "n_q_heads", "n_kv_heads", "head_dim", "nbits", "group_size",
+                                               "residual_length", "res_rows", "res_capacity", "new_rows")] + [("scaling", ctypes.c_float)] + [
+        (n, ctypes.c_int64) for n in ("q_stride_b", "q_stride_h", "q_stride_l", "new_stride_b", "new_stride_h", "new_stride_l",
+                                      "res_stride_b", "res_stride_h", "out_stride_b", "out_stride_h", "out_stride_l")]
 
 
 _lib = None
@@ -120,6 +142,12 @@ def lib():
         L.kvc_merge_workspace_bytes.restype = sz
         L.kvc_merge_pivot.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         L.kvc_think_prune.argtypes = [ctypes.POINTER(ThinkParams), vp, vp, vp, vp, vp, vp]
+        qp, qs, dq = ctypes.POINTER(QuantParams), ctypes.POINTER(QuantSeg), ctypes.POINTER(DecodeQuantParams)
+        L.kvc_quantize_rows.argtypes = [qp, vp, vp, vp, vp]
+        L.kvc_dequantize_rows.argtypes = [qp, vp, vp, vp, vp]
+        L.kvc_decode_quant_workspace_bytes.argtypes = [dq, qs, qs]
+        L.kvc_decode_quant_workspace_bytes.restype = sz
+        L.kvc_decode_step_quant.argtypes = [dq, qs, qs] + [vp] * 7 + [sz, vp]
         _lib = L
     return _lib
 
@@ -360,6 +388,97 @@ def decode_step(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail
     _check(_call(dev, lib().kvc_decode_step2, ctypes.byref(p), ctypes.byref(x), _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(k_prefix),
                  _ptr(v_prefix), _ptr(k_tail), _ptr(v_tail), _ptr(k_pruned if pruned_rows else None), _ptr(chan if pruned_rows else None),
                  _ptr(out), _ptr(ws), nbytes, _stream(dev)))
+    return out
+
+
+QUANT_KEYS, QUANT_VALUES = 0, 1
+
+
+def quant_buffers(bsz, n_heads, capacity, head_dim, nbits, group_size, device):
+    """Empty buffers of one quantized segment (include/kvc.h layout): key codes, value codes, key metadata
+    [b, H, ceil(capacity / G), 2, D] and value metadata [b, H, capacity, D / G, 2]."""
+    kc = torch.empty(bsz, n_heads, capacity, head_dim * nbits // 8, dtype=torch.uint8, device=device)
+    km = torch.empty(bsz, n_heads, -(-capacity // group_size), 2, head_dim, dtype=torch.float32, device=device)
+    vm = torch.empty(bsz, n_heads, capacity, head_dim // group_size, 2, dtype=torch.float32, device=device)
+    return kc, torch.empty_like(kc), km, vm
+
+
+def _quant_params(mode, dtype, b, h, D, nbits, group_size, row0, rows, codes, meta, st):
+    p = QuantParams()
+    p.dtype, p.bsz, p.n_heads, p.head_dim, p.nbits, p.group_size = DTYPES[dtype], b, h, D, nbits, group_size
+    p.mode, p.row0, p.rows, p.capacity = mode, row0, rows, codes.shape[2]
+    p.src_stride_b, p.src_stride_h, p.src_stride_l = st
+    assert codes.dtype == torch.uint8 and meta.dtype == torch.float32 and codes.stride(2) == codes.shape[3] and codes.stride(3) == 1
+    p.code_stride_b, p.code_stride_h = codes.stride(0), codes.stride(1)
+    p.meta_stride_b, p.meta_stride_h = meta.stride(0), meta.stride(1)
+    return p
+
+
+def quantize_rows(src, codes, meta, row0, mode, nbits, group_size):
+    """kvc_quantize_rows: src [b, H, rows, D] (any strides, last dim contiguous) -> rows [row0, row0 + rows) of the segment
+    buffers `codes` and `meta` (the key or the value metadata, by `mode`; quant_buffers)."""
+    _require_gpu(src, codes, meta)
+    dev = _one_device(src, codes, meta)
+    src = _last_dim_contig(src)
+    b, h, n, D = src.shape
+    p = _quant_params(mode, src.dtype, b, h, D, nbits, group_size, row0, n, codes, meta, (src.stride(0), src.stride(1), src.stride(2)))
+    _check(_call(dev, lib().kvc_quantize_rows, ctypes.byref(p), _ptr(src), _ptr(codes), _ptr(meta), _stream(dev)))
+
+
+def dequantize_rows(codes, meta, row0, rows, mode, nbits, group_size, dtype):
+    """kvc_dequantize_rows: rows [row0, row0 + rows) of a segment -> a new [b, H, rows, D] tensor of `dtype`."""
+    _require_gpu(codes, meta)
+    dev = _one_device(codes, meta)
+    b, h, _, cb = codes.shape
+    D = cb * 8 // nbits
+    out = torch.empty(b, h, rows, D, dtype=dtype, device=dev)
+    p = _quant_params(mode, dtype, b, h, D, nbits, group_size, row0, rows, codes, meta, (out.stride(0), out.stride(1), out.stride(2)))
+    _check(_call(dev, lib().kvc_dequantize_rows, ctypes.byref(p), _ptr(codes), _ptr(meta), _ptr(out), _stream(dev)))
+    return out
+
+
+def _quant_seg(seg):
+    """(k_codes, v_codes, k_meta, v_meta, rows) or None -> kvc_quant_seg."""
+    s = QuantSeg()
+    if seg is None:
+        return s
+    kc, vc, km, vm, rows = seg
+    assert kc.stride() == vc.stride() and kc.dtype == vc.dtype == torch.uint8
+    s.k_codes, s.v_codes, s.k_meta, s.v_meta = kc.data_ptr(), vc.data_ptr(), km.data_ptr(), vm.data_ptr()
+    s.rows, s.capacity = rows, kc.shape[2]
+    s.code_stride_b, s.code_stride_h = kc.stride(0), kc.stride(1)
+    s.k_meta_stride_b, s.k_meta_stride_h, s.v_meta_stride_b, s.v_meta_stride_h = km.stride(0), km.stride(1), vm.stride(0), vm.stride(1)
+    return s
+
+
+def decode_step_quant(q, k_new, v_new, prefix, qtail, k_res, v_res, res_rows, scaling, nbits, group_size, residual_length):
+    """One decode step over the quantized cache (kvc_decode_step_quant): k_new / v_new [b, H_kv, t, D] are appended to the residual
+    buffers [b, H_kv, capacity, D] at row res_rows and the attention output [b, t, H_q, D] of q [b, H_q, t, D] over the quantized
+    prefix (per query head), the quantized tail (per KV head) and the residual comes back.  prefix / qtail: (k_codes, v_codes,
+    k_meta, v_meta, rows) of quant_buffers, or None for an empty segment."""
+    _require_gpu(q, k_new, v_new, k_res, v_res)
+    dev = _one_device(q, k_new, v_new, k_res, v_res, *(prefix[:4] if prefix else ()), *(qtail[:4] if qtail else ()))
+    q, k_new, v_new = _last_dim_contig(q), _last_dim_contig(k_new), _last_dim_contig(v_new)
+    if k_new.stride() != v_new.stride():
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    b, hq, t, D = q.shape
+    assert k_new.shape == v_new.shape and k_new.shape[2] == t and k_res.stride() == v_res.stride()
+    assert k_res.stride(3) == 1 and k_res.stride(2) == D, "residual rows must be dense"
+    out = torch.empty(b, t, hq, D, dtype=q.dtype, device=dev)
+    p = DecodeQuantParams()
+    p.dtype, p.bsz, p.n_q_heads, p.n_kv_heads, p.head_dim = DTYPES[q.dtype], b, hq, k_new.shape[1], D
+    p.nbits, p.group_size, p.residual_length = nbits, group_size, residual_length
+    p.res_rows, p.res_capacity, p.new_rows, p.scaling = res_rows, k_res.shape[2], t, scaling
+    p.q_stride_b, p.q_stride_h, p.q_stride_l = q.stride(0), q.stride(1), q.stride(2)
+    p.new_stride_b, p.new_stride_h, p.new_stride_l = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    p.res_stride_b, p.res_stride_h = k_res.stride(0), k_res.stride(1)
+    p.out_stride_b, p.out_stride_h, p.out_stride_l = out.stride(0), out.stride(2), out.stride(1)
+    sp, st = _quant_seg(prefix), _quant_seg(qtail)
+    L = lib()
+    nbytes = L.kvc_decode_quant_workspace_bytes(ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st))
+    ws = workspace(dev, nbytes) if nbytes else None
+    _check(_call(dev, L.kvc_decode_step_quant, ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st), _ptr(q), _ptr(k_new), _ptr(v_new),
+                 _ptr(k_res), _ptr(v_res), _ptr(out), _ptr(ws), nbytes, _stream(dev)))
     return out
 
 

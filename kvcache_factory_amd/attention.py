@@ -25,7 +25,7 @@ import torch
 from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
 
 from . import pyramidkv_utils as pu
-from .cache import CompressedDynamicLayer, RaggedDynamicLayer, ThinkDynamicLayer
+from .cache import CompressedDynamicLayer, QuantizedCompressedCache, RaggedDynamicLayer, ThinkDynamicLayer
 
 _INIT = {
     "pyramidkv": lambda self: pu.init_pyramidkv(self, num_hidden_layers=self.config.num_hidden_layers),
@@ -73,6 +73,13 @@ def _fusable(module, layer, hidden_states, attention_mask, kwargs):
             and module.head_dim in (64, 128) and not kwargs.get("output_attentions", False)
             and getattr(module.config, "sliding_window", None) is None
             and hidden_states.dtype in (torch.bfloat16, torch.float16, torch.float32))
+
+
+def _refuse_quantized(cache, method):
+    """AdaKV / HeadKV / ThinK keep caches of their own layer types; a quantized cache's layers are not silently replaced."""
+    if isinstance(cache, QuantizedCompressedCache):
+        raise NotImplementedError(f"kvcache_factory_amd: {method} keeps its own cache layout; QuantizedCompressedCache is built for "
+                                  "the SnapKV / PyramidKV / H2O / StreamingLLM / L2Norm / CAM / fullkv paths only")
 
 
 def _pending_for(cache):
@@ -172,6 +179,7 @@ def make_ragged_forward(method, apply_rotary_pos_emb, eager_attention_forward, r
     init = pu.init_adakv if method == "adakv" else pu.init_headkv
 
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+        _refuse_quantized(past_key_values, method)
         init(self)
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)
@@ -217,6 +225,7 @@ def make_think_forward(apply_rotary_pos_emb, eager_attention_forward, repeat_kv)
     recent + decoded rows] in one kvc_decode_step2 call (the reference: two matmuls, cat, softmax, matmul, :175-196)."""
 
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+        _refuse_quantized(past_key_values, "think")
         pu.init_think(self)
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)

@@ -6,7 +6,7 @@ cache stores `cap` tokens per head, but RoPE positions / cache_position for the 
 the real prompt length.  transformers 5.x derives both from `layer.get_seq_length()`, so the layer keeps them apart.
 """
 import torch
-from transformers.cache_utils import DynamicLayer
+from transformers.cache_utils import Cache, DynamicLayer
 
 
 def _placeholder_only(name):
@@ -213,6 +213,219 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
     def get_mask_sizes(self, query_length):
         # the mask must be as wide as what attention will really see: stored tokens + the new ones
         return self.stored_length() + query_length, 0
+
+
+def _check_quant_args(nbits, q_group_size, residual_length):
+    if nbits not in (2, 4, 8):
+        raise ValueError(f"nbits must be 2, 4 or 8, got {nbits}")
+    if q_group_size not in (32, 64, 128):
+        raise ValueError(f"q_group_size must be 32, 64 or 128, got {q_group_size}")
+    if residual_length < q_group_size or residual_length % q_group_size:
+        raise ValueError(f"residual_length must be a positive multiple of q_group_size ({q_group_size}), got {residual_length}")
+
+
+class QuantizedCompressedLayer(CompressedDynamicLayer):
+    """A compressed layer whose cache is stored quantized (KIVI-style; the reference's `--quant_method kivi --nbits N`, which
+    hands generate() transformers' quantized cache).  The rule, the packing and the metadata are those of include/kvc.h: keys
+    per channel over groups of G stored rows, values per token over groups of G channels, asymmetric round-to-nearest in fp32.
+
+    Segments:  PREFIX — the compressed prompt (k + W rows per query head), quantized once at the layer's first decode step
+    (the grouped prefill flush writes K' / V' on a side stream, so this happens on the current stream after it has settled) —
+    the full-precision prompt buffers are dropped then;  QUANTIZED TAIL — decoded rows, append-only: a block, once quantized,
+    is never re-quantized;  RESIDUAL — full-precision decoded rows.  After every step, once the residual holds at least
+    R = residual_length rows, its oldest floor(rows / G) * G rows are quantized onto the tail and the rest move to the front.
+
+    This departs on purpose from transformers' QuantizedLayer, which de-quantizes and re-quantizes the WHOLE cache every time
+    its residual fills: that costs time proportional to the cache and compounds the rounding error.  The reference's own
+    quantizers (HQQ's optimiser, quanto's MaxOptimizer) are not reproduced, so its bytes are not claimed.
+
+    Two forms, as in CompressedDynamicLayer, and one per generation (switching raises RuntimeError):  FUSED (`decode_attend`,
+    kvc_decode_step_quant) — tail and residual per KV head, one kernel over all four segments;  REFERENCE-SHAPED (`update`,
+    taken when the fused step does not apply: bsz > 1 / beams, output_attentions, DECODE_KERNEL = 0) — tail and residual per
+    incoming head, returns cat(de-quantized prefix, de-quantized tail, residual + new rows).  A layer that never went through
+    `prefill` (fullkv) takes its first `update` as the prefix and returns those inputs unquantized, as transformers does."""
+
+    RES_SPARE = 64                      # residual rows beyond residual_length (the step's new rows land there)
+
+    def __init__(self, nbits=4, q_group_size=64, residual_length=128):
+        _check_quant_args(nbits, q_group_size, residual_length)
+        super().__init__()
+        self.nbits, self.group_size, self.residual_length = nbits, q_group_size, residual_length
+        self._clear_quant()
+
+    def _clear_quant(self):
+        self._pkc = self._pvc = self._pkm = self._pvm = None     # prefix: codes [b, H, P, D*nbits/8], metadata (kvc.h)
+        self._tkc = self._tvc = self._tkm = self._tvm = None     # quantized tail, same layout, capacity rows per head
+        self._rk = self._rv = None                               # residual [b, H, capacity, D], full precision
+        self._prows = self._trows = self._rrows = 0
+        self._mode = None                                        # None, "fused" or "shaped"
+
+    _batch_tensors = CompressedDynamicLayer._batch_tensors + ("_pkc", "_pvc", "_pkm", "_pvm", "_tkc", "_tvc", "_tkm", "_tvm", "_rk", "_rv")
+
+    def reset(self):
+        super().reset()
+        self._clear_quant()
+
+    def prefill(self, k_compressed, v_compressed, true_length):
+        self._clear_quant()
+        super().prefill(k_compressed, v_compressed, true_length)
+
+    # ---- segments ------------------------------------------------------------------------------------------------------
+    def _seg(self, which):
+        if which == "prefix":
+            return None if self._pkc is None else (self._pkc, self._pvc, self._pkm, self._pvm, self._prows)
+        return None if self._tkc is None else (self._tkc, self._tvc, self._tkm, self._tvm, self._trows)
+
+    def _quantize_into(self, k, v, bufs, row0):
+        from . import _kvc
+        kc, vc, km, vm = bufs
+        _kvc.quantize_rows(k, kc, km, row0, _kvc.QUANT_KEYS, self.nbits, self.group_size)
+        _kvc.quantize_rows(v, vc, vm, row0, _kvc.QUANT_VALUES, self.nbits, self.group_size)
+
+    def _set_prefix(self, k, v):
+        from . import _kvc
+        b, h, n, d = k.shape
+        bufs = _kvc.quant_buffers(b, h, n, d, self.nbits, self.group_size, k.device)
+        self._quantize_into(k, v, bufs, 0)
+        self._pkc, self._pvc, self._pkm, self._pvm = bufs
+        self._prows = n
+
+    def _quantize_prefix(self):
+        """The compressed prompt -> the quantized prefix; the full-precision prompt buffers go."""
+        if self._pkc is None and self._kbuf is not None:
+            self._set_prefix(self._kbuf[:, :, :self._stored], self._vbuf[:, :, :self._stored])
+            self._kbuf = self._vbuf = None
+            self._stored = 0
+
+    def _ensure_residual(self, like, t):
+        b, h, _, d = like.shape
+        if self._rk is None:
+            self._rk = torch.empty(b, h, self.residual_length + max(self.RES_SPARE, t), d, dtype=like.dtype, device=like.device)
+            self._rv = torch.empty_like(self._rk)
+        elif self._rrows + t > self._rk.shape[2]:
+            rk = torch.empty(b, h, self._rrows + t + self.RES_SPARE, d, dtype=self._rk.dtype, device=self._rk.device)
+            rv = torch.empty_like(rk)
+            rk[:, :, :self._rrows].copy_(self._rk[:, :, :self._rrows])
+            rv[:, :, :self._rrows].copy_(self._rv[:, :, :self._rrows])
+            self._rk, self._rv = rk, rv
+
+    def _flush(self):
+        """Once the residual holds >= R rows: its oldest floor(rows / G) * G rows onto the quantized tail, the rest to the front."""
+        from . import _kvc
+        if self._rrows < self.residual_length:
+            return
+        G = self.group_size
+        n = self._rrows // G * G
+        b, h, _, d = self._rk.shape
+        need = self._trows + n
+        if self._tkc is None or need > self._tkc.shape[2]:                # grow: capacity doubles, quantized bytes are copied as they are
+            cap = max(need, 4 * self.residual_length, 0 if self._tkc is None else 2 * self._tkc.shape[2])
+            bufs = _kvc.quant_buffers(b, h, cap, d, self.nbits, G, self._rk.device)
+            if self._tkc is not None and self._trows:
+                for new, old, rows in zip(bufs, (self._tkc, self._tvc, self._tkm, self._tvm),
+                                          (self._trows, self._trows, self._trows // G, self._trows)):
+                    new[:, :, :rows].copy_(old[:, :, :rows])
+            self._tkc, self._tvc, self._tkm, self._tvm = bufs
+        self._quantize_into(self._rk[:, :, :n], self._rv[:, :, :n], (self._tkc, self._tvc, self._tkm, self._tvm), self._trows)
+        rest = self._rrows - n
+        if rest:
+            self._rk[:, :, :rest] = self._rk[:, :, n:n + rest].clone()
+            self._rv[:, :, :rest] = self._rv[:, :, n:n + rest].clone()
+        self._trows, self._rrows = need, rest
+
+    def _enter(self, mode):
+        if self._mode is not None and self._mode != mode:
+            raise RuntimeError(f"kvcache_factory_amd: this quantized layer decodes in the {self._mode} form; it cannot switch to the "
+                               f"{mode} form in the middle of a generation (bsz, output_attentions and DECODE_KERNEL must stay as they were)")
+        self._mode = mode
+
+    # ---- the reference's view ------------------------------------------------------------------------------------------
+    def _qview(self, which):
+        from . import _kvc
+        if self._pkc is None:                                   # prompt not quantized yet: the compressed prompt as it was written
+            buf = self._kbuf if which == "k" else self._vbuf
+            return None if buf is None else buf[:, :, :self._stored]
+        k = which == "k"
+        mode = _kvc.QUANT_KEYS if k else _kvc.QUANT_VALUES
+        parts = [_kvc.dequantize_rows(self._pkc if k else self._pvc, self._pkm if k else self._pvm, 0, self._prows, mode, self.nbits,
+                                      self.group_size, self.dtype)]
+        hq = parts[0].shape[1]
+        if self._trows:
+            t = _kvc.dequantize_rows(self._tkc if k else self._tvc, self._tkm if k else self._tvm, 0, self._trows, mode, self.nbits,
+                                     self.group_size, self.dtype)
+            parts.append(t.repeat_interleave(hq // t.shape[1], dim=1))
+        if self._rrows:
+            r = (self._rk if k else self._rv)[:, :, :self._rrows]
+            parts.append(r.repeat_interleave(hq // r.shape[1], dim=1))
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=2)
+
+    keys = property(lambda self: self._qview("k"), _placeholder_only("keys"))
+    values = property(lambda self: self._qview("v"), _placeholder_only("values"))
+
+    # ---- decode: the reference-shaped path -----------------------------------------------------------------------------
+    def update(self, key_states, value_states, *args, **kwargs):
+        if not self.is_initialized:
+            self.lazy_initialization(key_states, value_states)
+        t = key_states.shape[-2]
+        if self._pkc is None and self._kbuf is None:            # a layer that never went through prefill(): this is the prefix
+            self._set_prefix(key_states, value_states)
+            self.true_length += t
+            return key_states, value_states
+        self._enter("shaped")
+        self._quantize_prefix()
+        self._ensure_residual(key_states, t)
+        self._rk[:, :, self._rrows:self._rrows + t].copy_(key_states)
+        self._rv[:, :, self._rrows:self._rrows + t].copy_(value_states)
+        self._rrows += t
+        self.true_length += t
+        k, v = self.keys, self.values
+        self._flush()
+        return k, v
+
+    # ---- decode: the fused step ----------------------------------------------------------------------------------------
+    def decode_attend(self, query_states, key_states, value_states, scaling):
+        """One decode step (kvc_decode_step_quant): the step's rows [bsz, H_kv, t, D] go to the residual and the attention output
+        [bsz, t, H_q, D] over quantized prefix, quantized tail and residual comes back; then the residual flush rule."""
+        from . import _kvc
+        self._enter("fused")
+        self._quantize_prefix()
+        t = key_states.shape[-2]
+        self._ensure_residual(key_states, t)
+        out = _kvc.decode_step_quant(query_states, key_states, value_states, self._seg("prefix"), self._seg("tail"), self._rk, self._rv,
+                                     self._rrows, scaling, self.nbits, self.group_size, self.residual_length)
+        self._rrows += t
+        self.true_length += t
+        self._flush()
+        return out
+
+    def can_split(self):
+        return self._pkc is not None or self._kbuf is not None
+
+    # ---- bookkeeping ---------------------------------------------------------------------------------------------------
+    def stored_length(self):
+        pre = self._prows if self._pkc is not None else (self._stored if self._kbuf is not None else 0)
+        return pre + self._trows + self._rrows
+
+
+class QuantizedCompressedCache(Cache):
+    """A transformers Cache of QuantizedCompressedLayer, one per hidden layer: the compressed prompt and the decoded tokens are
+    stored at `nbits` bits (2, 4 or 8), keys grouped per channel and values per token in groups of `q_group_size`, the last
+    < residual_length decoded tokens in full precision.  The keyword names are those of transformers' QuantizedCache, so the
+    reference's `cache_config` values carry over:
+
+        model.generate(ids, past_key_values=QuantizedCompressedCache(model.config, nbits=2))
+
+    `backend`, `axis_key` and `axis_value` are refused: the grouping here is fixed (KIVI's)."""
+
+    def __init__(self, config, nbits=4, q_group_size=64, residual_length=128, backend=None, axis_key=None, axis_value=None):
+        for name, val in (("backend", backend), ("axis_key", axis_key), ("axis_value", axis_value)):
+            if val is not None:
+                raise ValueError(f"QuantizedCompressedCache: `{name}` is not configurable — keys are quantized per channel and values "
+                                 "per token with this library's own HIP kernels (include/kvc.h)")
+        _check_quant_args(nbits, q_group_size, residual_length)
+        text = config.get_text_config() if hasattr(config, "get_text_config") else config
+        self.nbits, self.q_group_size, self.residual_length = nbits, q_group_size, residual_length
+        super().__init__(layers=[QuantizedCompressedLayer(nbits, q_group_size, residual_length) for _ in range(text.num_hidden_layers)])
 
 
 class RaggedDynamicLayer(_BatchOps, DynamicLayer):

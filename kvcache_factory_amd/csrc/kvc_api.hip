@@ -564,6 +564,175 @@ __attribute__((visibility("default"))) int kvc_decode_step2(const kvc_decode_par
     return decode_run(p, ext, q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, k_pruned, chan, out, workspace, workspace_bytes, hip_stream);
 }
 
+// ---- quantized decode cache (kvc_quant.hip) -------------------------------------------------------------------------------
+namespace {
+int quant_common(int dtype, int head_dim, int nbits, int group) {
+    if (dtype < KVC_BF16 || dtype > KVC_FP32) return fail(KVC_ERR_INVALID, "unknown dtype %d", dtype);
+    if (head_dim != 64 && head_dim != 128) return fail(KVC_ERR_UNSUPPORTED, "quantized cache kernels are built for head_dim 64 and 128, got %d", head_dim);
+    if (nbits != 2 && nbits != 4 && nbits != 8) return fail(KVC_ERR_INVALID, "nbits must be 2, 4 or 8, got %d", nbits);
+    if (group != 32 && group != 64 && group != 128) return fail(KVC_ERR_UNSUPPORTED, "group_size must be 32, 64 or 128, got %d", group);
+    if (head_dim % group) return fail(KVC_ERR_INVALID, "group_size %d does not divide head_dim %d", group, head_dim);
+    return KVC_OK;
+}
+inline int64_t kmeta_floats(int rows, int group, int head_dim) { return (int64_t)((rows + group - 1) / group) * 2 * head_dim; }
+inline int64_t vmeta_floats(int rows, int group, int head_dim) { return (int64_t)rows * (head_dim / group) * 2; }
+
+int quant_check(const kvc_quant_params* p) {
+    if (!p) return fail(KVC_ERR_INVALID, "params is NULL");
+    if (int rc = quant_common(p->dtype, p->head_dim, p->nbits, p->group_size)) return rc;
+    if (p->mode != KVC_QUANT_KEYS && p->mode != KVC_QUANT_VALUES) return fail(KVC_ERR_INVALID, "unknown mode %d", p->mode);
+    if (p->bsz < 1 || p->n_heads < 1) return fail(KVC_ERR_INVALID, "bsz / n_heads must be positive");
+    if (p->rows < 0 || p->row0 < 0 || p->capacity < 0 || (int64_t)p->row0 + p->rows > p->capacity)
+        return fail(KVC_ERR_INVALID, "rows [%d, %d + %d) do not fit a capacity of %d", p->row0, p->row0, p->rows, p->capacity);
+    if (p->mode == KVC_QUANT_KEYS && p->row0 % p->group_size)
+        return fail(KVC_ERR_INVALID, "key rows start at a group boundary: row0 %d is not a multiple of group_size %d", p->row0, p->group_size);
+    const int64_t cb = (int64_t)p->head_dim * p->nbits / 8;
+    const int64_t mf = p->mode == KVC_QUANT_KEYS ? kmeta_floats(p->capacity, p->group_size, p->head_dim) : vmeta_floats(p->capacity, p->group_size, p->head_dim);
+    if (p->code_stride_h < (int64_t)p->capacity * cb || p->code_stride_b < p->n_heads * p->code_stride_h)
+        return fail(KVC_ERR_INVALID, "code strides (%lld, %lld) smaller than the %d rows of %lld bytes per head", (long long)p->code_stride_b,
+                    (long long)p->code_stride_h, p->capacity, (long long)cb);
+    if (p->meta_stride_h < mf || p->meta_stride_b < p->n_heads * p->meta_stride_h)
+        return fail(KVC_ERR_INVALID, "metadata strides (%lld, %lld) smaller than the %lld floats per head", (long long)p->meta_stride_b,
+                    (long long)p->meta_stride_h, (long long)mf);
+    if (p->src_stride_l < p->head_dim || p->src_stride_h < 0 || p->src_stride_b < 0)   // any [b][h][row] order, rows apart
+        return fail(KVC_ERR_INVALID, "source / destination strides do not hold rows of head_dim %d", p->head_dim);
+    const int ma = p->mode == KVC_QUANT_KEYS ? 4 : 2;              // key metadata is read as float4, value metadata as float2
+    if (p->code_stride_b % 16 || p->code_stride_h % 16 || p->meta_stride_b % ma || p->meta_stride_h % ma)
+        return fail(KVC_ERR_ALIGNMENT, "code strides must be multiples of 16 bytes and metadata strides of %d floats", ma);
+    return KVC_OK;
+}
+kvc::QuantArgs quant_args(const kvc_quant_params* p) {
+    kvc::QuantArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.s_stride_b = p->src_stride_b; a.s_stride_h = p->src_stride_h; a.s_stride_l = p->src_stride_l;
+    a.c_stride_b = p->code_stride_b; a.c_stride_h = p->code_stride_h; a.m_stride_b = p->meta_stride_b; a.m_stride_h = p->meta_stride_h;
+    a.bsz = p->bsz; a.n_heads = p->n_heads; a.head_dim = p->head_dim; a.group = p->group_size; a.row0 = p->row0; a.rows = p->rows;
+    return a;
+}
+
+int seg_check(const char* what, const kvc_quant_seg* s, int n_heads, int head_dim, int nbits, int group) {
+    if (!s) return fail(KVC_ERR_INVALID, "%s segment is NULL", what);
+    if (s->rows < 0 || s->capacity < s->rows) return fail(KVC_ERR_INVALID, "%s: %d rows do not fit a capacity of %d", what, s->rows, s->capacity);
+    const int64_t cb = (int64_t)head_dim * nbits / 8;
+    if (s->code_stride_h < (int64_t)s->capacity * cb || s->code_stride_b < n_heads * s->code_stride_h ||
+        s->k_meta_stride_h < kmeta_floats(s->capacity, group, head_dim) || s->k_meta_stride_b < n_heads * s->k_meta_stride_h ||
+        s->v_meta_stride_h < vmeta_floats(s->capacity, group, head_dim) || s->v_meta_stride_b < n_heads * s->v_meta_stride_h)
+        return fail(KVC_ERR_INVALID, "%s: strides smaller than a capacity of %d rows", what, s->capacity);
+    if (s->code_stride_b % 16 || s->code_stride_h % 16 || s->k_meta_stride_b % 4 || s->k_meta_stride_h % 4 ||
+        s->v_meta_stride_b % 2 || s->v_meta_stride_h % 2)
+        return fail(KVC_ERR_ALIGNMENT, "%s: code strides must be multiples of 16 bytes, key / value metadata strides of 4 / 2 floats", what);
+    return KVC_OK;
+}
+int decode_quant_check(const kvc_decode_quant_params* p, const kvc_quant_seg* pre, const kvc_quant_seg* qt) {
+    if (!p) return fail(KVC_ERR_INVALID, "params is NULL");
+    if (int rc = quant_common(p->dtype, p->head_dim, p->nbits, p->group_size)) return rc;
+    if (p->residual_length < p->group_size || p->residual_length % p->group_size)
+        return fail(KVC_ERR_INVALID, "residual_length %d must be a positive multiple of group_size %d", p->residual_length, p->group_size);
+    if (p->bsz < 1 || p->n_q_heads < 1 || p->n_kv_heads < 1 || p->n_q_heads % p->n_kv_heads)
+        return fail(KVC_ERR_INVALID, "bsz / head counts invalid");
+    if (p->new_rows < 1 || p->res_rows < 0 || p->res_rows >= p->residual_length)
+        return fail(KVC_ERR_INVALID, "new_rows must be >= 1 and res_rows in [0, residual_length): got %d, %d", p->new_rows, p->res_rows);
+    if ((int64_t)p->res_rows + p->new_rows > p->res_capacity)
+        return fail(KVC_ERR_INVALID, "%d residual rows + %d new rows do not fit a capacity of %d", p->res_rows, p->new_rows, p->res_capacity);
+    if (p->res_stride_h < (int64_t)p->res_capacity * p->head_dim || p->res_stride_b < p->n_kv_heads * p->res_stride_h)
+        return fail(KVC_ERR_INVALID, "residual strides smaller than its capacity");
+    if (int rc = seg_check("prefix", pre, p->n_q_heads, p->head_dim, p->nbits, p->group_size)) return rc;
+    if (int rc = seg_check("quantized tail", qt, p->n_kv_heads, p->head_dim, p->nbits, p->group_size)) return rc;
+    if (qt->rows % p->group_size) return fail(KVC_ERR_INVALID, "quantized tail rows %d not a multiple of group_size %d", qt->rows, p->group_size);
+    return KVC_OK;
+}
+int decode_quant_splits(const kvc_decode_quant_params* p, const kvc_quant_seg* pre, const kvc_quant_seg* qt) {
+    return kvc::decode_splits(p->bsz, p->n_q_heads, p->new_rows, pre->rows + qt->rows + p->res_rows + p->new_rows);
+}
+}  // namespace
+
+extern "C" {
+__attribute__((visibility("default"))) int kvc_quantize_rows(const kvc_quant_params* p, const void* src, uint8_t* codes, float* meta, void* hip_stream) {
+    if (int rc = quant_check(p)) return rc;
+    if (p->rows == 0) return KVC_OK;
+    if (!src || !codes || !meta) return fail(KVC_ERR_INVALID, "src, codes and meta must be non-NULL");
+    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)src) % esize_of(p->dtype))
+        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, src element-aligned");
+    kvc::QuantArgs a = quant_args(p);
+    a.src = src; a.codes = codes; a.meta = meta;
+    if (int rc = kvc::launch_quantize(a, p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
+    return hip_ok("quantize launch");
+}
+
+__attribute__((visibility("default"))) int kvc_dequantize_rows(const kvc_quant_params* p, const uint8_t* codes, const float* meta, void* dst, void* hip_stream) {
+    if (int rc = quant_check(p)) return rc;
+    if (p->rows == 0) return KVC_OK;
+    if (!dst || !codes || !meta) return fail(KVC_ERR_INVALID, "codes, meta and dst must be non-NULL");
+    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)dst) % esize_of(p->dtype))
+        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, dst element-aligned");
+    kvc::QuantArgs a = quant_args(p);
+    a.dst = dst; a.codes_in = codes; a.meta_in = meta;
+    if (int rc = kvc::launch_dequantize(a, p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no de-quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
+    return hip_ok("dequantize launch");
+}
+
+__attribute__((visibility("default"))) size_t kvc_decode_quant_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix,
+                                                                               const kvc_quant_seg* qtail) {
+    if (decode_quant_check(p, prefix, qtail)) return 0;
+    return kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, decode_quant_splits(p, prefix, qtail));
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_quant(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail,
+                                                                 const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
+                                                                 void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = decode_quant_check(p, prefix, qtail)) return rc;
+    if (!q || !k_new || !v_new || !k_res || !v_res || !out)
+        return fail(KVC_ERR_INVALID, "q, k_new, v_new, k_res, v_res and out must be non-NULL");
+    for (const kvc_quant_seg* s : {prefix, qtail})
+        if (s->rows > 0 && (!s->k_codes || !s->v_codes || !s->k_meta || !s->v_meta))
+            return fail(KVC_ERR_INVALID, "a segment with rows needs its codes and metadata");
+    const int es = esize_of(p->dtype);
+    const void* ptrs[] = {q, k_new, v_new, k_res, v_res, out, prefix->k_codes, prefix->v_codes, prefix->k_meta, prefix->v_meta,
+                          qtail->k_codes, qtail->v_codes, qtail->k_meta, qtail->v_meta};
+    for (const void* ptr : ptrs) if (((uintptr_t)ptr) % 16) return fail(KVC_ERR_ALIGNMENT, "a pointer is not 16-byte aligned");
+    const int64_t strides[] = {p->q_stride_b, p->q_stride_h, p->q_stride_l, p->new_stride_b, p->new_stride_h, p->new_stride_l,
+                               p->res_stride_b, p->res_stride_h};
+    for (int64_t sd : strides) if ((sd * es) % 16) return fail(KVC_ERR_ALIGNMENT, "a stride is not a multiple of 16 bytes");
+    kvc::DecodeArgs ap;                                           // append to the residual; combine of the splits
+    std::memset(&ap, 0, sizeof(ap));
+    ap.k_new = k_new; ap.v_new = v_new; ap.k_tail = k_res; ap.v_tail = v_res; ap.out = out;
+    ap.new_stride_b = p->new_stride_b; ap.new_stride_h = p->new_stride_h; ap.new_stride_l = p->new_stride_l;
+    ap.tail_stride_b = p->res_stride_b; ap.tail_stride_h = p->res_stride_h;
+    ap.out_stride_b = p->out_stride_b; ap.out_stride_h = p->out_stride_h; ap.out_stride_l = p->out_stride_l;
+    ap.bsz = p->bsz; ap.n_q_heads = p->n_q_heads; ap.n_kv_heads = p->n_kv_heads; ap.group = p->n_q_heads / p->n_kv_heads;
+    ap.tail_rows = p->res_rows; ap.new_rows = p->new_rows; ap.esize = es; ap.row_bytes = p->head_dim * es;
+    kvc::DecodeQArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.q = q; a.k_res = k_res; a.v_res = v_res; a.out = out;
+    a.q_stride_b = p->q_stride_b; a.q_stride_h = p->q_stride_h; a.q_stride_l = p->q_stride_l;
+    a.res_stride_b = p->res_stride_b; a.res_stride_h = p->res_stride_h;
+    a.out_stride_b = p->out_stride_b; a.out_stride_h = p->out_stride_h; a.out_stride_l = p->out_stride_l;
+    kvc::QSegArgs* dst[2] = {&a.pre, &a.qt};
+    const kvc_quant_seg* src[2] = {prefix, qtail};
+    for (int k = 0; k < 2; ++k) {
+        kvc::QSegArgs& d = *dst[k];
+        const kvc_quant_seg& s = *src[k];
+        d.kc = s.k_codes; d.vc = s.v_codes; d.km = s.k_meta; d.vm = s.v_meta; d.rows = s.rows;
+        d.c_stride_b = s.code_stride_b; d.c_stride_h = s.code_stride_h;
+        d.km_stride_b = s.k_meta_stride_b; d.km_stride_h = s.k_meta_stride_h; d.vm_stride_b = s.v_meta_stride_b; d.vm_stride_h = s.v_meta_stride_h;
+    }
+    a.bsz = p->bsz; a.n_q_heads = p->n_q_heads; a.group = p->n_q_heads / p->n_kv_heads; a.gsize = p->group_size;
+    a.res_rows = p->res_rows; a.new_rows = p->new_rows; a.scaling = p->scaling;
+    a.splits = 1;
+    if (workspace) {
+        if (((uintptr_t)workspace) % 16) return fail(KVC_ERR_ALIGNMENT, "workspace is not 16-byte aligned");
+        int s = decode_quant_splits(p, prefix, qtail);
+        while (s > 1 && kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, s) > workspace_bytes) --s;
+        a.splits = s; a.part = static_cast<float*>(workspace);
+    }
+    if (int rc = kvc::launch_decode_step_quant(a, p->dtype, p->head_dim, p->nbits, ap, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no quantized decode kernel for dtype %d head_dim %d nbits %d", p->dtype, p->head_dim, p->nbits);
+    return hip_ok("quantized decode step launch");
+}
+}  // extern "C"
+
 // ---- AdaKV / HeadKV -------------------------------------------------------------------------------------------------------
 namespace {
 struct RaggedLayout { size_t ratio, idx, sort, flat, top, sel, total; };

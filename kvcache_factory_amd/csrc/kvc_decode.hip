@@ -206,4 +206,19 @@ int launch_decode_step(DecodeArgs a, int dtype, int head_dim, hipStream_t st) {
     return KVC_ERR_UNSUPPORTED;
 }
 
+// The quantized decode step (kvc_quant.hip) appends to its residual and merges its splits with these two kernels.
+int launch_decode_append(const DecodeArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(decode_append_kernel, dim3((unsigned)a.new_rows, (unsigned)(a.bsz * a.n_kv_heads), 2), dim3(64), 0, st, a);
+    return 0;
+}
+
+int launch_decode_combine(const DecodeArgs& a, int dtype, int head_dim, hipStream_t st) {
+    const dim3 cgrid((unsigned)(a.bsz * a.n_q_heads), (unsigned)a.new_rows);
+#define KVC_CASE(DT_, D_) if (dtype == DT_ && head_dim == D_) { hipLaunchKernelGGL((decode_combine_kernel<DT_, D_>), cgrid, dim3(D_), 0, st, a); return 0; }
+    KVC_CASE(KVC_BF16, 128) KVC_CASE(KVC_BF16, 64) KVC_CASE(KVC_FP16, 128) KVC_CASE(KVC_FP16, 64)
+    KVC_CASE(KVC_FP32, 128) KVC_CASE(KVC_FP32, 64)
+#undef KVC_CASE
+    return KVC_ERR_UNSUPPORTED;
+}
+
 }  // namespace kvc

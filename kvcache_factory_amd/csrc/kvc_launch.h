@@ -164,6 +164,28 @@ struct DecodeArgs {        // one decode step over the compacted cache (kvc_deco
     float* part; int splits, rows_per_split;          // workspace: (m, l, acc[D]) per (b, h, token, split)
 };
 
+struct QuantArgs {         // kvc_quant.hip: quantize / de-quantize rows [row0, row0 + rows) of one segment (include/kvc.h layout)
+    const void* src; void* dst;                       // [b][h][row][D] elements (quantize reads src, de-quantize writes dst)
+    uint8_t* codes; const uint8_t* codes_in; float* meta; const float* meta_in;
+    int64_t s_stride_b, s_stride_h, s_stride_l, c_stride_b, c_stride_h, m_stride_b, m_stride_h;
+    int bsz, n_heads, head_dim, group, row0, rows;
+};
+
+struct QSegArgs {          // one quantized segment of the decode cache
+    const uint8_t* kc; const uint8_t* vc; const float* km; const float* vm;
+    int64_t c_stride_b, c_stride_h, km_stride_b, km_stride_h, vm_stride_b, vm_stride_h;
+    int rows;
+};
+
+struct DecodeQArgs {       // kvc_decode_step_quant: quantized prefix + quantized tail + residual (+ the step's rows)
+    const void* q; const void* k_res; const void* v_res; void* out;
+    int64_t q_stride_b, q_stride_h, q_stride_l, res_stride_b, res_stride_h, out_stride_b, out_stride_h, out_stride_l;
+    QSegArgs pre, qt;                                 // prefix per query head, quantized tail per KV head
+    int bsz, n_q_heads, group, gsize, res_rows, new_rows;
+    float scaling;
+    float* part; int splits, rows_per_split;          // as DecodeArgs: (m, l, acc[D]) per (b, h, token, split)
+};
+
 // Raise a kernel's dynamic-LDS limit above 64 KB once per (kernel instantiation, device): `cache` is a function-local
 // static array owned by the caller.  Never called again on the launch path, so launches stay graph-capturable.
 struct LdsCache { size_t ok[16]; };
@@ -200,6 +222,11 @@ struct CamArgs {           // CAM (kvc_cam.hip)
 int launch_cam_prob(const CamArgs& a, int dtype, hipStream_t st);
 int launch_cam_merge(const CamArgs& a, int dtype, int head_dim, hipStream_t st);
 int launch_decode_step(DecodeArgs a, int dtype, int head_dim, hipStream_t st);
+int launch_decode_append(const DecodeArgs& a, hipStream_t st);                       // the step's rows -> tail (kvc_decode.hip)
+int launch_decode_combine(const DecodeArgs& a, int dtype, int head_dim, hipStream_t st);   // splits -> out (kvc_decode.hip)
+int launch_quantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
+int launch_dequantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
+int launch_decode_step_quant(DecodeQArgs a, int dtype, int head_dim, int nbits, const DecodeArgs& append, hipStream_t st);
 int decode_splits(int bsz, int n_q_heads, int new_rows, int rows);
 size_t decode_part_bytes(int bsz, int n_q_heads, int new_rows, int head_dim, int splits);
 int launch_sort_prefix(const RaggedSortArgs& a, int dtype, void* scratch, hipStream_t st);
