@@ -305,6 +305,45 @@ int kvc_decode_step_quant(const kvc_decode_quant_params* p, const kvc_quant_seg*
                           const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
                           void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
 
+/* ---- quantized cache with exact outliers (KVQuant-style "dense-and-sparse", --quant_method kvquant) ------------------------
+ * Split: T' = threshold rounded to dtype (round to nearest even; fp32 uses it as is).  Element x is an OUTLIER iff x < -T' or
+ * x > T' (so +-inf are outliers and NaN is not).  The DENSE input is x with every outlier replaced by +0; its codes and metadata
+ * follow the rule above unchanged (the zeros take part in their group's min / max).  De-quantized value: x'' = x at an outlier,
+ * otherwise x' = fmaf(code, scale, mn).  Groups holding +-inf are therefore well defined; groups with NaN stay unspecified.
+ *
+ * Sparse layout, one POOL per (segment, keys or values), indexed by the batch row like every other buffer:
+ *   chan    [b][pool_capacity] uint8     channel of the entry
+ *   val     [b][pool_capacity] dtype     its exact value
+ *   used    [b] int32                    entries handed out so far (device counter)
+ *   rowinfo [b][h][capacity] uint32      per segment row: (first entry << 8) | count; 0 = no entries
+ * A quantize call lays its entries out in (h, row, channel) order starting at used[b] and advances used[b] by the number of
+ * outliers it found.  A row whose entries do not all fit below pool_capacity gets rowinfo 0 and no entry is written for it (no
+ * byte at or past pool_capacity is ever written); used[b] still advances by the full count, so used[b] > pool_capacity tells the
+ * caller that the call overflowed and must be repeated into a larger pool (rows that fit are complete).  pool_capacity < 2^24.
+ * All four entry points below are enqueue-only (no allocation, no copy to the host, no synchronisation). */
+typedef struct kvc_quant_outliers {
+    uint8_t* chan; void* val; int32_t* used; uint32_t* rowinfo;
+    int32_t pool_capacity, reserved;
+    int64_t pool_stride_b;                                  /* entries between batch rows of chan / val (>= pool_capacity) */
+    int64_t rowinfo_stride_b, rowinfo_stride_h;             /* words (rowinfo_stride_h >= the segment's capacity) */
+} kvc_quant_outliers;
+
+/* As kvc_quantize_rows, with the split: dense codes / metadata, plus the outliers of rows [row0, row0 + rows) into `outl`
+ * (rowinfo of those rows, entries from used[b]).  threshold: finite and > 0. */
+int kvc_quantize_rows_outliers(const kvc_quant_params* p, float threshold, const void* src, uint8_t* codes, float* meta,
+                               const kvc_quant_outliers* outl, void* hip_stream);
+/* As kvc_dequantize_rows, then the outliers of those rows written back exactly. */
+int kvc_dequantize_rows_outliers(const kvc_quant_params* p, const uint8_t* codes, const float* meta, const kvc_quant_outliers* outl,
+                                 void* dst, void* hip_stream);
+/* kvc_decode_step_quant over segments with outliers: prefix_outl / qtail_outl point at TWO descriptors each (keys, then values;
+ * rowinfo per query head for the prefix, per KV head for the tail).  A segment without rows needs none (NULL allowed). */
+size_t kvc_decode_quant_outliers_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail,
+                                                 const kvc_quant_outliers* prefix_outl, const kvc_quant_outliers* qtail_outl);
+int kvc_decode_step_quant_outliers(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail,
+                                   const kvc_quant_outliers* prefix_outl, const kvc_quant_outliers* qtail_outl,
+                                   const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
+                                   void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
+
 /* ---- AdaKV / HeadKV: per-head budgets, ragged ("flattened") cache -----------------------------------
  * Replaces AdaKVCluster.update_kv (pyramidkv_utils.py:674-757), HeadKVCluster.update_kv (:813-878) and, at decode, the
  * repo's native update_flatten_view (csrc/csrc/cuda_api.cu:12-85) + flash_attn_varlen_func (llama_model.py:2363-2390).

@@ -9,7 +9,7 @@ All compute runs in hand-written HIP kernels (csrc/, libkvc_hip.so) through the 
 there is no CPU or eager-PyTorch fallback: if the extension is missing the import of `_kvc` raises.
 """
 __version__ = "0.1.0"
-__all__ = ["QuantizedCompressedCache", "QuantizedCompressedLayer"]
+__all__ = ["QuantizedCompressedCache", "QuantizedCompressedLayer", "KVQuantCompressedCache", "KVQuantCompressedLayer"]
 
 
 def __getattr__(name):

@@ -28,7 +28,8 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_ragged_compact", "kvc_ragged_decode_step", "kvc_l2norm_workspace_bytes", "kvc_l2norm_compress",
            "kvc_merge_workspace_bytes", "kvc_merge_pivot", "kvc_think_prune", "kvc_decode_workspace_bytes", "kvc_decode_step2",
            "kvc_cam_workspace_bytes", "kvc_cam_plan", "kvc_cam_merge", "kvc_quantize_rows", "kvc_dequantize_rows",
-           "kvc_decode_quant_workspace_bytes", "kvc_decode_step_quant")
+           "kvc_decode_quant_workspace_bytes", "kvc_decode_step_quant", "kvc_quantize_rows_outliers",
+           "kvc_dequantize_rows_outliers", "kvc_decode_quant_outliers_workspace_bytes", "kvc_decode_step_quant_outliers")
 
 
 class KvcError(RuntimeError):
@@ -93,6 +94,12 @@ class DecodeQuantParams(ctypes.Structure):
                                       "res_stride_b", "res_stride_h", "out_stride_b", "out_stride_h", "out_stride_l")]
 
 
+class QuantOutliers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("chan", "val", "used", "rowinfo")] + [
+        ("pool_capacity", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+        (n, ctypes.c_int64) for n in ("pool_stride_b", "rowinfo_stride_b", "rowinfo_stride_h")]
+
+
 _lib = None
 
 
@@ -148,6 +155,12 @@ def lib():
         L.kvc_decode_quant_workspace_bytes.argtypes = [dq, qs, qs]
         L.kvc_decode_quant_workspace_bytes.restype = sz
         L.kvc_decode_step_quant.argtypes = [dq, qs, qs] + [vp] * 7 + [sz, vp]
+        qo = ctypes.POINTER(QuantOutliers)
+        L.kvc_quantize_rows_outliers.argtypes = [qp, ctypes.c_float, vp, vp, vp, qo, vp]
+        L.kvc_dequantize_rows_outliers.argtypes = [qp, vp, vp, qo, vp, vp]
+        L.kvc_decode_quant_outliers_workspace_bytes.argtypes = [dq, qs, qs, qo, qo]
+        L.kvc_decode_quant_outliers_workspace_bytes.restype = sz
+        L.kvc_decode_step_quant_outliers.argtypes = [dq, qs, qs, qo, qo] + [vp] * 7 + [sz, vp]
         _lib = L
     return _lib
 
@@ -479,6 +492,87 @@ def decode_step_quant(q, k_new, v_new, prefix, qtail, k_res, v_res, res_rows, sc
     ws = workspace(dev, nbytes) if nbytes else None
     _check(_call(dev, L.kvc_decode_step_quant, ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st), _ptr(q), _ptr(k_new), _ptr(v_new),
                  _ptr(k_res), _ptr(v_res), _ptr(out), _ptr(ws), nbytes, _stream(dev)))
+    return out
+
+
+def outlier_pool(bsz, n_heads, capacity, pool_capacity, dtype, device):
+    """Empty outlier pool of one segment and mode (include/kvc.h, kvc_quant_outliers): (chan [b, pool_capacity] uint8,
+    val [b, pool_capacity] dtype, used [b] int32 = 0, rowinfo [b, H, capacity] int32 holding the uint32 words)."""
+    return (torch.empty(bsz, pool_capacity, dtype=torch.uint8, device=device), torch.empty(bsz, pool_capacity, dtype=dtype, device=device),
+            torch.zeros(bsz, dtype=torch.int32, device=device), torch.empty(bsz, n_heads, capacity, dtype=torch.int32, device=device))
+
+
+def _outliers(pool):
+    o = QuantOutliers()
+    chan, val, used, ri = pool
+    assert chan.shape == val.shape and chan.stride() == val.stride() and used.dtype == ri.dtype == torch.int32 and ri.stride(2) == 1
+    o.chan, o.val, o.used, o.rowinfo = chan.data_ptr(), val.data_ptr(), used.data_ptr(), ri.data_ptr()
+    o.pool_capacity, o.pool_stride_b = chan.shape[1], chan.stride(0)
+    o.rowinfo_stride_b, o.rowinfo_stride_h = ri.stride(0), ri.stride(1)
+    return o
+
+
+def outlier_threshold(threshold, dtype):
+    """T' of include/kvc.h: the threshold rounded to the cache dtype exactly as torch rounds a Python float it compares with."""
+    return float(torch.tensor(float(threshold), dtype=dtype)) if dtype != torch.float32 else float(threshold)
+
+
+def quantize_rows_outliers(src, codes, meta, pool, row0, mode, nbits, group_size, threshold):
+    """kvc_quantize_rows_outliers: as quantize_rows with the outliers (|x| > T') zeroed in the codes and laid out in `pool`
+    (outlier_pool) from its used[b] on.  Enqueue-only: pool[2] (used) > pool capacity afterwards means the call overflowed."""
+    _require_gpu(src, codes, meta, *pool)
+    dev = _one_device(src, codes, meta, *pool)
+    src = _last_dim_contig(src)
+    b, h, n, D = src.shape
+    assert pool[1].dtype == src.dtype and pool[3].shape[2] == codes.shape[2]
+    p = _quant_params(mode, src.dtype, b, h, D, nbits, group_size, row0, n, codes, meta, (src.stride(0), src.stride(1), src.stride(2)))
+    o = _outliers(pool)
+    _check(_call(dev, lib().kvc_quantize_rows_outliers, ctypes.byref(p), ctypes.c_float(outlier_threshold(threshold, src.dtype)),
+                 _ptr(src), _ptr(codes), _ptr(meta), ctypes.byref(o), _stream(dev)))
+
+
+def dequantize_rows_outliers(codes, meta, pool, row0, rows, mode, nbits, group_size, dtype):
+    """kvc_dequantize_rows_outliers: rows [row0, row0 + rows) -> a new [b, H, rows, D] tensor, outliers exact."""
+    _require_gpu(codes, meta, *pool)
+    dev = _one_device(codes, meta, *pool)
+    b, h, _, cb = codes.shape
+    D = cb * 8 // nbits
+    out = torch.empty(b, h, rows, D, dtype=dtype, device=dev)
+    p = _quant_params(mode, dtype, b, h, D, nbits, group_size, row0, rows, codes, meta, (out.stride(0), out.stride(1), out.stride(2)))
+    o = _outliers(pool)
+    _check(_call(dev, lib().kvc_dequantize_rows_outliers, ctypes.byref(p), _ptr(codes), _ptr(meta), ctypes.byref(o), _ptr(out), _stream(dev)))
+    return out
+
+
+def decode_step_quant_outliers(q, k_new, v_new, prefix, qtail, prefix_outl, qtail_outl, k_res, v_res, res_rows, scaling, nbits, group_size,
+                               residual_length):
+    """decode_step_quant over segments with exact outliers (kvc_decode_step_quant_outliers); prefix_outl / qtail_outl: (key pool,
+    value pool) of outlier_pool, or None for an empty segment."""
+    _require_gpu(q, k_new, v_new, k_res, v_res)
+    dev = _one_device(q, k_new, v_new, k_res, v_res, *(prefix[:4] if prefix else ()), *(qtail[:4] if qtail else ()))
+    q, k_new, v_new = _last_dim_contig(q), _last_dim_contig(k_new), _last_dim_contig(v_new)
+    if k_new.stride() != v_new.stride():
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    b, hq, t, D = q.shape
+    assert k_new.shape == v_new.shape and k_new.shape[2] == t and k_res.stride() == v_res.stride()
+    assert k_res.stride(3) == 1 and k_res.stride(2) == D, "residual rows must be dense"
+    out = torch.empty(b, t, hq, D, dtype=q.dtype, device=dev)
+    p = DecodeQuantParams()
+    p.dtype, p.bsz, p.n_q_heads, p.n_kv_heads, p.head_dim = DTYPES[q.dtype], b, hq, k_new.shape[1], D
+    p.nbits, p.group_size, p.residual_length = nbits, group_size, residual_length
+    p.res_rows, p.res_capacity, p.new_rows, p.scaling = res_rows, k_res.shape[2], t, scaling
+    p.q_stride_b, p.q_stride_h, p.q_stride_l = q.stride(0), q.stride(1), q.stride(2)
+    p.new_stride_b, p.new_stride_h, p.new_stride_l = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    p.res_stride_b, p.res_stride_h = k_res.stride(0), k_res.stride(1)
+    p.out_stride_b, p.out_stride_h, p.out_stride_l = out.stride(0), out.stride(2), out.stride(1)
+    sp, st = _quant_seg(prefix), _quant_seg(qtail)
+    po = (QuantOutliers * 2)(*(_outliers(x) for x in prefix_outl)) if prefix_outl else None
+    to = (QuantOutliers * 2)(*(_outliers(x) for x in qtail_outl)) if qtail_outl else None
+    L = lib()
+    nbytes = L.kvc_decode_quant_outliers_workspace_bytes(ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st), po, to)
+    ws = workspace(dev, nbytes) if nbytes else None
+    _check(_call(dev, L.kvc_decode_step_quant_outliers, ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st), po, to, _ptr(q), _ptr(k_new),
+                 _ptr(v_new), _ptr(k_res), _ptr(v_res), _ptr(out), _ptr(ws), nbytes, _stream(dev)))
     return out
 
 

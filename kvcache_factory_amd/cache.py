@@ -276,7 +276,7 @@ class QuantizedCompressedLayer(CompressedDynamicLayer):
             return None if self._pkc is None else (self._pkc, self._pvc, self._pkm, self._pvm, self._prows)
         return None if self._tkc is None else (self._tkc, self._tvc, self._tkm, self._tvm, self._trows)
 
-    def _quantize_into(self, k, v, bufs, row0):
+    def _quantize_into(self, k, v, bufs, row0, seg=None):
         from . import _kvc
         kc, vc, km, vm = bufs
         _kvc.quantize_rows(k, kc, km, row0, _kvc.QUANT_KEYS, self.nbits, self.group_size)
@@ -286,7 +286,7 @@ class QuantizedCompressedLayer(CompressedDynamicLayer):
         from . import _kvc
         b, h, n, d = k.shape
         bufs = _kvc.quant_buffers(b, h, n, d, self.nbits, self.group_size, k.device)
-        self._quantize_into(k, v, bufs, 0)
+        self._quantize_into(k, v, bufs, 0, "prefix")
         self._pkc, self._pvc, self._pkm, self._pvm = bufs
         self._prows = n
 
@@ -318,20 +318,27 @@ class QuantizedCompressedLayer(CompressedDynamicLayer):
         n = self._rrows // G * G
         b, h, _, d = self._rk.shape
         need = self._trows + n
-        if self._tkc is None or need > self._tkc.shape[2]:                # grow: capacity doubles, quantized bytes are copied as they are
-            cap = max(need, 4 * self.residual_length, 0 if self._tkc is None else 2 * self._tkc.shape[2])
-            bufs = _kvc.quant_buffers(b, h, cap, d, self.nbits, G, self._rk.device)
-            if self._tkc is not None and self._trows:
-                for new, old, rows in zip(bufs, (self._tkc, self._tvc, self._tkm, self._tvm),
-                                          (self._trows, self._trows, self._trows // G, self._trows)):
-                    new[:, :, :rows].copy_(old[:, :, :rows])
-            self._tkc, self._tvc, self._tkm, self._tvm = bufs
-        self._quantize_into(self._rk[:, :, :n], self._rv[:, :, :n], (self._tkc, self._tvc, self._tkm, self._tvm), self._trows)
+        if self._tkc is None or need > self._tkc.shape[2]:
+            self._grow_tail(need)
+        self._quantize_into(self._rk[:, :, :n], self._rv[:, :, :n], (self._tkc, self._tvc, self._tkm, self._tvm), self._trows, "tail")
         rest = self._rrows - n
         if rest:
             self._rk[:, :, :rest] = self._rk[:, :, n:n + rest].clone()
             self._rv[:, :, :rest] = self._rv[:, :, n:n + rest].clone()
         self._trows, self._rrows = need, rest
+
+    def _grow_tail(self, need):
+        """Quantized tail capacity for `need` rows: capacity doubles, quantized bytes are copied as they are."""
+        from . import _kvc
+        G = self.group_size
+        b, h, _, d = self._rk.shape
+        cap = max(need, 4 * self.residual_length, 0 if self._tkc is None else 2 * self._tkc.shape[2])
+        bufs = _kvc.quant_buffers(b, h, cap, d, self.nbits, G, self._rk.device)
+        if self._tkc is not None and self._trows:
+            for new, old, rows in zip(bufs, (self._tkc, self._tvc, self._tkm, self._tvm),
+                                      (self._trows, self._trows, self._trows // G, self._trows)):
+                new[:, :, :rows].copy_(old[:, :, :rows])
+        self._tkc, self._tvc, self._tkm, self._tvm = bufs
 
     def _enter(self, mode):
         if self._mode is not None and self._mode != mode:
@@ -346,18 +353,24 @@ class QuantizedCompressedLayer(CompressedDynamicLayer):
             buf = self._kbuf if which == "k" else self._vbuf
             return None if buf is None else buf[:, :, :self._stored]
         k = which == "k"
-        mode = _kvc.QUANT_KEYS if k else _kvc.QUANT_VALUES
-        parts = [_kvc.dequantize_rows(self._pkc if k else self._pvc, self._pkm if k else self._pvm, 0, self._prows, mode, self.nbits,
-                                      self.group_size, self.dtype)]
+        parts = [self._dequant("prefix", k, self._prows)]
         hq = parts[0].shape[1]
         if self._trows:
-            t = _kvc.dequantize_rows(self._tkc if k else self._tvc, self._tkm if k else self._tvm, 0, self._trows, mode, self.nbits,
-                                     self.group_size, self.dtype)
+            t = self._dequant("tail", k, self._trows)
             parts.append(t.repeat_interleave(hq // t.shape[1], dim=1))
         if self._rrows:
             r = (self._rk if k else self._rv)[:, :, :self._rrows]
             parts.append(r.repeat_interleave(hq // r.shape[1], dim=1))
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=2)
+
+    def _dequant(self, seg, k, rows):
+        from . import _kvc
+        mode = _kvc.QUANT_KEYS if k else _kvc.QUANT_VALUES
+        if seg == "prefix":
+            codes, meta = (self._pkc, self._pkm) if k else (self._pvc, self._pvm)
+        else:
+            codes, meta = (self._tkc, self._tkm) if k else (self._tvc, self._tvm)
+        return _kvc.dequantize_rows(codes, meta, 0, rows, mode, self.nbits, self.group_size, self.dtype)
 
     keys = property(lambda self: self._qview("k"), _placeholder_only("keys"))
     values = property(lambda self: self._qview("v"), _placeholder_only("values"))
@@ -391,12 +404,16 @@ class QuantizedCompressedLayer(CompressedDynamicLayer):
         self._quantize_prefix()
         t = key_states.shape[-2]
         self._ensure_residual(key_states, t)
-        out = _kvc.decode_step_quant(query_states, key_states, value_states, self._seg("prefix"), self._seg("tail"), self._rk, self._rv,
-                                     self._rrows, scaling, self.nbits, self.group_size, self.residual_length)
+        out = self._decode_step(query_states, key_states, value_states, scaling)
         self._rrows += t
         self.true_length += t
         self._flush()
         return out
+
+    def _decode_step(self, query_states, key_states, value_states, scaling):
+        from . import _kvc
+        return _kvc.decode_step_quant(query_states, key_states, value_states, self._seg("prefix"), self._seg("tail"), self._rk, self._rv,
+                                      self._rrows, scaling, self.nbits, self.group_size, self.residual_length)
 
     def can_split(self):
         return self._pkc is not None or self._kbuf is not None
@@ -593,3 +610,181 @@ class ThinkDynamicLayer(_BatchOps, DynamicLayer):
 
     def get_mask_sizes(self, query_length):
         return self.stored_length() + query_length, 0
+
+
+def _check_threshold(outlier_threshold):
+    t = float(outlier_threshold)
+    if not (t > 0.0 and t != float("inf")):
+        raise ValueError(f"outlier_threshold must be finite and > 0, got {outlier_threshold}")
+    return t
+
+
+_POOL_PARTS = ("chan", "val", "used", "ri")
+
+
+class KVQuantCompressedLayer(QuantizedCompressedLayer):
+    """QuantizedCompressedLayer with exact outliers (KVQuant's dense-and-sparse split; the reference's `--quant_method kvquant`):
+    every element with |x| > T' (T' = outlier_threshold rounded to the cache dtype) is zeroed in the quantized (dense) part and kept
+    exactly in an outlier POOL, one per segment and per keys / values (include/kvc.h: chan, val, used, rowinfo; all indexed by the
+    batch row, so beam reordering permutes them like every other buffer).  De-quantized cache = the KIVI values with the outliers
+    written back.  Segments, forms and the residual flush are QuantizedCompressedLayer's.
+
+    Host reads of the device counters `used` all go through `_read_used`:
+      PREFIX — the prompt is quantized into a pool of an estimated size (1/32 of its elements) and `used` is read back once (the
+               layer's first decode step, or the prompt's `update` for fullkv); an overflow repeats the call into a pool of the
+               exact size, a smaller count shrinks the pool to it (capacity: max_b used rounded up to 16, at least 16);
+      TAIL   — a flush of n rows adds at most W = n * D * H entries per batch row.  The host keeps an upper bound of used (+W per
+               flush).  After every flush max_b used is also copied to pinned host memory without waiting (an event marks its
+               arrival); the next flush takes that value as its bound if it has arrived, which it normally has R tokens later.  The
+               true value is read (blocking) only when bound + W would pass the pool capacity; the pool then grows (entries copied
+               byte for byte) whenever fewer than W entries are left.  New tail pools hold 2W entries."""
+
+    PREFIX_EST = 32                     # the prompt's pool is first sized at 1/PREFIX_EST of its elements
+
+    def __init__(self, nbits=4, q_group_size=64, residual_length=128, outlier_threshold=6.0):
+        self.outlier_threshold = _check_threshold(outlier_threshold)
+        super().__init__(nbits, q_group_size, residual_length)
+
+    def _clear_quant(self):
+        super()._clear_quant()
+        for pool in ("_pko", "_pvo", "_tko", "_tvo"):          # prefix / tail pools of keys / values
+            self._set_pool(pool, None)
+        self._tbound = 0                                      # upper bound of max_b used[b] of the tail pools
+        self._note = None                                     # (host copy of max_b used after the last flush, its event)
+
+    _batch_tensors = QuantizedCompressedLayer._batch_tensors + tuple(
+        f"{pool}_{part}" for pool in ("_pko", "_pvo", "_tko", "_tvo") for part in _POOL_PARTS)
+
+    def _pool(self, name):
+        parts = tuple(getattr(self, f"{name}_{p}") for p in _POOL_PARTS)
+        return None if parts[0] is None else parts
+
+    def _set_pool(self, name, pool):
+        for p, t in zip(_POOL_PARTS, pool if pool is not None else (None,) * 4):
+            setattr(self, f"{name}_{p}", t)
+
+    def _read_used(self, *pools):
+        """The one place where the host waits for the device: max over the batch of each pool's `used`."""
+        return [int(x) for x in torch.stack([p[2] for p in pools]).amax(dim=1).tolist()]
+
+    def _note_used(self, pools):
+        """After a flush: max_b used of the tail pools on its way to the host, without waiting."""
+        u = torch.stack([p[2] for p in pools]).amax()
+        if u.is_cuda:
+            if getattr(self, "_used_host", None) is None:
+                self._used_host = torch.empty((), dtype=torch.int32, pin_memory=True)
+            self._used_host.copy_(u, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._note = (self._used_host, ev)
+        else:
+            self._note = (u.clone(), None)
+
+    def _take_note(self):
+        """The bound from the last flush's copy of used, if it has arrived (no waiting)."""
+        if self._note is not None and (self._note[1] is None or self._note[1].query()):
+            self._tbound = int(self._note[0])
+            self._note = None
+
+    # ---- quantize --------------------------------------------------------------------------------------------------------
+    def _quantize_pools(self, k, v, bufs, row0, pools):
+        from . import _kvc
+        kc, vc, km, vm = bufs
+        _kvc.quantize_rows_outliers(k, kc, km, pools[0], row0, _kvc.QUANT_KEYS, self.nbits, self.group_size, self.outlier_threshold)
+        _kvc.quantize_rows_outliers(v, vc, vm, pools[1], row0, _kvc.QUANT_VALUES, self.nbits, self.group_size, self.outlier_threshold)
+
+    @staticmethod
+    def _resized(pool, cap):
+        """The pool with `cap` entries per batch row: its first min(cap, old) entries copied byte for byte, used and rowinfo kept."""
+        chan, val, used, ri = pool
+        b, old = chan.shape
+        c2 = torch.empty(b, cap, dtype=chan.dtype, device=chan.device)
+        v2 = torch.empty(b, cap, dtype=val.dtype, device=val.device)
+        n = min(cap, old)
+        c2[:, :n].copy_(chan[:, :n])
+        v2[:, :n].copy_(val[:, :n])
+        return c2, v2, used, ri
+
+    def _quantize_into(self, k, v, bufs, row0, seg=None):
+        from . import _kvc
+        b, h, n, d = k.shape
+        if seg == "prefix":
+            est = max(16, -(-(h * n * d) // (16 * self.PREFIX_EST)) * 16)
+            pools = [_kvc.outlier_pool(b, h, n, est, k.dtype, k.device) for _ in range(2)]
+            self._quantize_pools(k, v, bufs, 0, pools)
+            used = self._read_used(*pools)
+            if max(used) > est:                                       # overflow: again, into pools of the exact size
+                pools = [_kvc.outlier_pool(b, h, n, max(16, -(-u // 16) * 16), k.dtype, k.device) for u in used]
+                self._quantize_pools(k, v, bufs, 0, pools)
+            else:
+                pools = [self._resized(p, max(16, -(-u // 16) * 16)) for p, u in zip(pools, used)]
+            self._set_pool("_pko", pools[0])
+            self._set_pool("_pvo", pools[1])
+            return
+        W = n * d * h                                                 # worst case of this flush, per batch row
+        pools = [self._pool("_tko"), self._pool("_tvo")]
+        cap = pools[0][0].shape[1]
+        self._take_note()
+        if self._tbound + W > cap:
+            self._tbound = max(self._read_used(*pools))
+            if self._tbound + W > cap:                                # grow: entries copied byte for byte
+                cap = max(2 * cap, self._tbound + 2 * W)
+                pools = [self._resized(p, cap) for p in pools]
+                self._set_pool("_tko", pools[0])
+                self._set_pool("_tvo", pools[1])
+        self._quantize_pools(k, v, bufs, row0, pools)
+        self._tbound += W
+        self._note_used(pools)
+
+    def _grow_tail(self, need):
+        from . import _kvc
+        old = self._trows
+        super()._grow_tail(need)
+        b, h, cap, _ = self._tkc.shape
+        if self._tko_chan is None:                                    # first flush: pools of two worst-case flushes
+            W = (need - old) * self._rk.shape[3] * h
+            for name in ("_tko", "_tvo"):
+                self._set_pool(name, _kvc.outlier_pool(b, h, cap, 2 * W, self._rk.dtype, self._rk.device))
+            self._tbound, self._note = 0, None
+            return
+        for name in ("_tko", "_tvo"):                                 # rowinfo follows the rows' capacity
+            chan, val, used, ri = self._pool(name)
+            r2 = torch.empty(b, h, cap, dtype=ri.dtype, device=ri.device)
+            r2[:, :, :old].copy_(ri[:, :, :old])
+            self._set_pool(name, (chan, val, used, r2))
+
+    # ---- de-quantize / decode ---------------------------------------------------------------------------------------------
+    def _dequant(self, seg, k, rows):
+        from . import _kvc
+        mode = _kvc.QUANT_KEYS if k else _kvc.QUANT_VALUES
+        if seg == "prefix":
+            codes, meta, pool = (self._pkc, self._pkm, self._pool("_pko")) if k else (self._pvc, self._pvm, self._pool("_pvo"))
+        else:
+            codes, meta, pool = (self._tkc, self._tkm, self._pool("_tko")) if k else (self._tvc, self._tvm, self._pool("_tvo"))
+        return _kvc.dequantize_rows_outliers(codes, meta, pool, 0, rows, mode, self.nbits, self.group_size, self.dtype)
+
+    def _decode_step(self, query_states, key_states, value_states, scaling):
+        from . import _kvc
+        po = (self._pool("_pko"), self._pool("_pvo")) if self._pkc is not None else None
+        to = (self._pool("_tko"), self._pool("_tvo")) if self._trows else None
+        return _kvc.decode_step_quant_outliers(query_states, key_states, value_states, self._seg("prefix"), self._seg("tail") if self._trows else None,
+                                               po, to, self._rk, self._rv, self._rrows, scaling, self.nbits, self.group_size,
+                                               self.residual_length)
+
+    def pool_bytes(self):
+        """Bytes held by the outlier pools (chan, val, used, rowinfo of every pool)."""
+        return sum(t.numel() * t.element_size() for n in self._batch_tensors if n.startswith(("_pko", "_pvo", "_tko", "_tvo"))
+                   for t in (getattr(self, n),) if t is not None)
+
+
+class KVQuantCompressedCache(QuantizedCompressedCache):
+    """QuantizedCompressedCache with exact outliers, one KVQuantCompressedLayer per hidden layer: the counterpart of the reference's
+    `--quant_method kvquant` (KVQuantizedCache(cache_config, outlier_threshold=6.0)).  The keyword names are the reference's:
+
+        model.generate(ids, past_key_values=KVQuantCompressedCache(model.config, nbits=2, outlier_threshold=6.0))"""
+
+    def __init__(self, config, nbits=4, q_group_size=64, residual_length=128, outlier_threshold=6.0, backend=None, axis_key=None,
+                 axis_value=None):
+        super().__init__(config, nbits, q_group_size, residual_length, backend, axis_key, axis_value)
+        self.outlier_threshold = _check_threshold(outlier_threshold)
+        self.layers = [KVQuantCompressedLayer(nbits, q_group_size, residual_length, self.outlier_threshold) for _ in self.layers]

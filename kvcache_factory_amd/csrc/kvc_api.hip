@@ -644,45 +644,10 @@ int decode_quant_check(const kvc_decode_quant_params* p, const kvc_quant_seg* pr
 int decode_quant_splits(const kvc_decode_quant_params* p, const kvc_quant_seg* pre, const kvc_quant_seg* qt) {
     return kvc::decode_splits(p->bsz, p->n_q_heads, p->new_rows, pre->rows + qt->rows + p->res_rows + p->new_rows);
 }
-}  // namespace
-
-extern "C" {
-__attribute__((visibility("default"))) int kvc_quantize_rows(const kvc_quant_params* p, const void* src, uint8_t* codes, float* meta, void* hip_stream) {
-    if (int rc = quant_check(p)) return rc;
-    if (p->rows == 0) return KVC_OK;
-    if (!src || !codes || !meta) return fail(KVC_ERR_INVALID, "src, codes and meta must be non-NULL");
-    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)src) % esize_of(p->dtype))
-        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, src element-aligned");
-    kvc::QuantArgs a = quant_args(p);
-    a.src = src; a.codes = codes; a.meta = meta;
-    if (int rc = kvc::launch_quantize(a, p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
-        return fail(rc, "no quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
-    return hip_ok("quantize launch");
-}
-
-__attribute__((visibility("default"))) int kvc_dequantize_rows(const kvc_quant_params* p, const uint8_t* codes, const float* meta, void* dst, void* hip_stream) {
-    if (int rc = quant_check(p)) return rc;
-    if (p->rows == 0) return KVC_OK;
-    if (!dst || !codes || !meta) return fail(KVC_ERR_INVALID, "codes, meta and dst must be non-NULL");
-    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)dst) % esize_of(p->dtype))
-        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, dst element-aligned");
-    kvc::QuantArgs a = quant_args(p);
-    a.dst = dst; a.codes_in = codes; a.meta_in = meta;
-    if (int rc = kvc::launch_dequantize(a, p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
-        return fail(rc, "no de-quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
-    return hip_ok("dequantize launch");
-}
-
-__attribute__((visibility("default"))) size_t kvc_decode_quant_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix,
-                                                                               const kvc_quant_seg* qtail) {
-    if (decode_quant_check(p, prefix, qtail)) return 0;
-    return kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, decode_quant_splits(p, prefix, qtail));
-}
-
-__attribute__((visibility("default"))) int kvc_decode_step_quant(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail,
-                                                                 const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
-                                                                 void* workspace, size_t workspace_bytes, void* hip_stream) {
-    if (int rc = decode_quant_check(p, prefix, qtail)) return rc;
+// The launch of kvc_decode_step_quant (o == nullptr) and of kvc_decode_step_quant_outliers: everything but the outlier descriptors.
+int decode_quant_run(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail, const kvc::DecodeOArgs* o,
+                     const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
+                     void* workspace, size_t workspace_bytes, void* hip_stream) {
     if (!q || !k_new || !v_new || !k_res || !v_res || !out)
         return fail(KVC_ERR_INVALID, "q, k_new, v_new, k_res, v_res and out must be non-NULL");
     for (const kvc_quant_seg* s : {prefix, qtail})
@@ -727,9 +692,179 @@ __attribute__((visibility("default"))) int kvc_decode_step_quant(const kvc_decod
         while (s > 1 && kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, s) > workspace_bytes) --s;
         a.splits = s; a.part = static_cast<float*>(workspace);
     }
-    if (int rc = kvc::launch_decode_step_quant(a, p->dtype, p->head_dim, p->nbits, ap, static_cast<hipStream_t>(hip_stream)))
-        return fail(rc, "no quantized decode kernel for dtype %d head_dim %d nbits %d", p->dtype, p->head_dim, p->nbits);
+    const int rc = o ? kvc::launch_decode_step_quant_outliers(a, *o, p->dtype, p->head_dim, p->nbits, ap, static_cast<hipStream_t>(hip_stream))
+                     : kvc::launch_decode_step_quant(a, p->dtype, p->head_dim, p->nbits, ap, static_cast<hipStream_t>(hip_stream));
+    if (rc) return fail(rc, "no quantized decode kernel for dtype %d head_dim %d nbits %d", p->dtype, p->head_dim, p->nbits);
     return hip_ok("quantized decode step launch");
+}
+}  // namespace
+
+extern "C" {
+__attribute__((visibility("default"))) int kvc_quantize_rows(const kvc_quant_params* p, const void* src, uint8_t* codes, float* meta, void* hip_stream) {
+    if (int rc = quant_check(p)) return rc;
+    if (p->rows == 0) return KVC_OK;
+    if (!src || !codes || !meta) return fail(KVC_ERR_INVALID, "src, codes and meta must be non-NULL");
+    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)src) % esize_of(p->dtype))
+        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, src element-aligned");
+    kvc::QuantArgs a = quant_args(p);
+    a.src = src; a.codes = codes; a.meta = meta;
+    if (int rc = kvc::launch_quantize(a, p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
+    return hip_ok("quantize launch");
+}
+
+__attribute__((visibility("default"))) int kvc_dequantize_rows(const kvc_quant_params* p, const uint8_t* codes, const float* meta, void* dst, void* hip_stream) {
+    if (int rc = quant_check(p)) return rc;
+    if (p->rows == 0) return KVC_OK;
+    if (!dst || !codes || !meta) return fail(KVC_ERR_INVALID, "codes, meta and dst must be non-NULL");
+    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)dst) % esize_of(p->dtype))
+        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, dst element-aligned");
+    kvc::QuantArgs a = quant_args(p);
+    a.dst = dst; a.codes_in = codes; a.meta_in = meta;
+    if (int rc = kvc::launch_dequantize(a, p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no de-quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
+    return hip_ok("dequantize launch");
+}
+
+__attribute__((visibility("default"))) size_t kvc_decode_quant_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix,
+                                                                               const kvc_quant_seg* qtail) {
+    if (decode_quant_check(p, prefix, qtail)) return 0;
+    return kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, decode_quant_splits(p, prefix, qtail));
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_quant(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail,
+                                                                 const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
+                                                                 void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = decode_quant_check(p, prefix, qtail)) return rc;
+    return decode_quant_run(p, prefix, qtail, nullptr, q, k_new, v_new, k_res, v_res, out, workspace, workspace_bytes, hip_stream);
+}
+}  // extern "C"
+
+// ---- quantized cache with exact outliers (kvc_quant.hip) -----------------------------------------------------------------
+namespace {
+constexpr int32_t kOutlPoolMax = (1 << 24) - 1;            // rowinfo keeps the first entry in 24 bits
+
+int outl_check(const char* what, const kvc_quant_outliers* o, int bsz, int n_heads, int capacity) {
+    if (!o) return fail(KVC_ERR_INVALID, "%s outlier descriptor is NULL", what);
+    if (o->pool_capacity < 0 || o->pool_capacity > kOutlPoolMax)
+        return fail(KVC_ERR_INVALID, "%s: pool_capacity %d outside [0, %d]", what, o->pool_capacity, kOutlPoolMax);
+    if (o->pool_stride_b < o->pool_capacity)
+        return fail(KVC_ERR_INVALID, "%s: pool_stride_b %lld smaller than pool_capacity %d", what, (long long)o->pool_stride_b, o->pool_capacity);
+    if (o->rowinfo_stride_h < capacity || o->rowinfo_stride_b < (int64_t)n_heads * o->rowinfo_stride_h)
+        return fail(KVC_ERR_INVALID, "%s: rowinfo strides (%lld, %lld) smaller than %d rows per head", what, (long long)o->rowinfo_stride_b,
+                    (long long)o->rowinfo_stride_h, capacity);
+    return KVC_OK;
+}
+int outl_ptrs(const char* what, const kvc_quant_outliers* o, int dtype) {
+    if (!o->used || !o->rowinfo || (o->pool_capacity > 0 && (!o->chan || !o->val)))
+        return fail(KVC_ERR_INVALID, "%s: used, rowinfo (and chan, val when pool_capacity > 0) must be non-NULL", what);
+    if (((uintptr_t)o->used) % 4 || ((uintptr_t)o->rowinfo) % 4 || ((uintptr_t)o->val) % esize_of(dtype))
+        return fail(KVC_ERR_ALIGNMENT, "%s: used / rowinfo must be 4-byte aligned, val element-aligned", what);
+    return KVC_OK;
+}
+int outl_threshold(float threshold, int dtype, float* rounded) {
+    if (!(threshold > 0.0f) || !std::isfinite(threshold)) return fail(KVC_ERR_INVALID, "threshold must be finite and > 0, got %g", (double)threshold);
+    if (dtype == KVC_BF16) {                                // round to nearest even (finite input: no NaN case)
+        uint32_t u;
+        std::memcpy(&u, &threshold, 4);
+        u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+        std::memcpy(rounded, &u, 4);
+    } else if (dtype == KVC_FP16) {
+        *rounded = (float)(_Float16)threshold;              // RNE; above the fp16 range: inf (nothing is an outlier then)
+    } else {
+        *rounded = threshold;
+    }
+    return KVC_OK;
+}
+kvc::OutlArgs outl_args(const kvc_quant_outliers* o, float thr) {
+    kvc::OutlArgs r;
+    std::memset(&r, 0, sizeof(r));
+    r.chan = o->chan; r.val = o->val; r.used = o->used; r.rowinfo = o->rowinfo;
+    r.pool_stride_b = o->pool_stride_b; r.ri_stride_b = o->rowinfo_stride_b; r.ri_stride_h = o->rowinfo_stride_h;
+    r.pool_capacity = o->pool_capacity; r.thr = thr;
+    return r;
+}
+int decode_outl_check(const kvc_decode_quant_params* p, const kvc_quant_seg* pre, const kvc_quant_seg* qt, const kvc_quant_outliers* po,
+                      const kvc_quant_outliers* to) {
+    if (int rc = decode_quant_check(p, pre, qt)) return rc;
+    if (pre->rows > 0) {
+        if (!po) return fail(KVC_ERR_INVALID, "prefix outlier descriptors are NULL");
+        for (int m = 0; m < 2; ++m) if (int rc = outl_check(m ? "prefix values" : "prefix keys", po + m, p->bsz, p->n_q_heads, pre->capacity)) return rc;
+    }
+    if (qt->rows > 0) {
+        if (!to) return fail(KVC_ERR_INVALID, "quantized tail outlier descriptors are NULL");
+        for (int m = 0; m < 2; ++m) if (int rc = outl_check(m ? "tail values" : "tail keys", to + m, p->bsz, p->n_kv_heads, qt->capacity)) return rc;
+    }
+    return KVC_OK;
+}
+}  // namespace
+
+extern "C" {
+__attribute__((visibility("default"))) int kvc_quantize_rows_outliers(const kvc_quant_params* p, float threshold, const void* src, uint8_t* codes,
+                                                                      float* meta, const kvc_quant_outliers* outl, void* hip_stream) {
+    if (int rc = quant_check(p)) return rc;
+    float thr = 0.0f;
+    if (int rc = outl_threshold(threshold, p->dtype, &thr)) return rc;
+    if (int rc = outl_check("outliers", outl, p->bsz, p->n_heads, p->capacity)) return rc;
+    if (p->rows == 0) return KVC_OK;
+    if (!src || !codes || !meta) return fail(KVC_ERR_INVALID, "src, codes and meta must be non-NULL");
+    if (int rc = outl_ptrs("outliers", outl, p->dtype)) return rc;
+    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)src) % esize_of(p->dtype))
+        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, src element-aligned");
+    kvc::QuantArgs a = quant_args(p);
+    a.src = src; a.codes = codes; a.meta = meta;
+    if (int rc = kvc::launch_quantize_outliers(a, outl_args(outl, thr), p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
+    return hip_ok("quantize (outliers) launch");
+}
+
+__attribute__((visibility("default"))) int kvc_dequantize_rows_outliers(const kvc_quant_params* p, const uint8_t* codes, const float* meta,
+                                                                        const kvc_quant_outliers* outl, void* dst, void* hip_stream) {
+    if (int rc = quant_check(p)) return rc;
+    if (int rc = outl_check("outliers", outl, p->bsz, p->n_heads, p->capacity)) return rc;
+    if (p->rows == 0) return KVC_OK;
+    if (!dst || !codes || !meta) return fail(KVC_ERR_INVALID, "codes, meta and dst must be non-NULL");
+    if (int rc = outl_ptrs("outliers", outl, p->dtype)) return rc;
+    if (((uintptr_t)codes) % 16 || ((uintptr_t)meta) % 16 || ((uintptr_t)dst) % esize_of(p->dtype))
+        return fail(KVC_ERR_ALIGNMENT, "codes / meta must be 16-byte aligned, dst element-aligned");
+    kvc::QuantArgs a = quant_args(p);
+    a.dst = dst; a.codes_in = codes; a.meta_in = meta;
+    if (int rc = kvc::launch_dequantize_outliers(a, outl_args(outl, 0.0f), p->dtype, p->nbits, p->mode, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no de-quantize kernel for dtype %d nbits %d", p->dtype, p->nbits);
+    return hip_ok("dequantize (outliers) launch");
+}
+
+__attribute__((visibility("default"))) size_t kvc_decode_quant_outliers_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix,
+                                                                                        const kvc_quant_seg* qtail, const kvc_quant_outliers* prefix_outl,
+                                                                                        const kvc_quant_outliers* qtail_outl) {
+    if (decode_outl_check(p, prefix, qtail, prefix_outl, qtail_outl)) return 0;
+    return kvc_decode_quant_workspace_bytes(p, prefix, qtail);
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_quant_outliers(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix,
+                                                                          const kvc_quant_seg* qtail, const kvc_quant_outliers* prefix_outl,
+                                                                          const kvc_quant_outliers* qtail_outl, const void* q, const void* k_new,
+                                                                          const void* v_new, void* k_res, void* v_res, void* out, void* workspace,
+                                                                          size_t workspace_bytes, void* hip_stream) {
+    if (int rc = decode_outl_check(p, prefix, qtail, prefix_outl, qtail_outl)) return rc;
+    kvc::DecodeOArgs o;
+    std::memset(&o, 0, sizeof(o));
+    const kvc_quant_seg* segs[2] = {prefix, qtail};
+    const kvc_quant_outliers* outs[2] = {prefix_outl, qtail_outl};
+    kvc::OSegArgs* dsts[2] = {&o.pre, &o.qt};
+    for (int k = 0; k < 2; ++k) {
+        if (segs[k]->rows == 0) continue;
+        const kvc_quant_outliers* ko = outs[k];
+        const kvc_quant_outliers* vo = outs[k] + 1;
+        for (const kvc_quant_outliers* x : {ko, vo})
+            if (int rc = outl_ptrs(k ? "tail outliers" : "prefix outliers", x, p->dtype)) return rc;
+        kvc::OSegArgs& d = *dsts[k];
+        d.kch = ko->chan; d.vch = vo->chan; d.kval = ko->val; d.vval = vo->val; d.kri = ko->rowinfo; d.vri = vo->rowinfo;
+        d.kpool_b = ko->pool_stride_b; d.vpool_b = vo->pool_stride_b;
+        d.kri_b = ko->rowinfo_stride_b; d.kri_h = ko->rowinfo_stride_h; d.vri_b = vo->rowinfo_stride_b; d.vri_h = vo->rowinfo_stride_h;
+        d.kcap = ko->pool_capacity; d.vcap = vo->pool_capacity;
+    }
+    return decode_quant_run(p, prefix, qtail, &o, q, k_new, v_new, k_res, v_res, out, workspace, workspace_bytes, hip_stream);
 }
 }  // extern "C"
 

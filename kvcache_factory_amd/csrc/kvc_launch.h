@@ -186,6 +186,20 @@ struct DecodeQArgs {       // kvc_decode_step_quant: quantized prefix + quantize
     float* part; int splits, rows_per_split;          // as DecodeArgs: (m, l, acc[D]) per (b, h, token, split)
 };
 
+struct OutlArgs {          // one outlier pool (include/kvc.h, kvc_quant_outliers) and the split threshold (already rounded to dtype)
+    uint8_t* chan; void* val; int32_t* used; uint32_t* rowinfo;
+    int64_t pool_stride_b, ri_stride_b, ri_stride_h;
+    int pool_capacity;
+    float thr;
+};
+
+struct OSegArgs {          // the key and value pools of one quantized segment, read by the decode step
+    const uint8_t* kch; const uint8_t* vch; const void* kval; const void* vval; const uint32_t* kri; const uint32_t* vri;
+    int64_t kpool_b, vpool_b, kri_b, kri_h, vri_b, vri_h;
+    int kcap, vcap;
+};
+struct DecodeOArgs { OSegArgs pre, qt; };
+
 // Raise a kernel's dynamic-LDS limit above 64 KB once per (kernel instantiation, device): `cache` is a function-local
 // static array owned by the caller.  Never called again on the launch path, so launches stay graph-capturable.
 struct LdsCache { size_t ok[16]; };
@@ -227,6 +241,10 @@ int launch_decode_combine(const DecodeArgs& a, int dtype, int head_dim, hipStrea
 int launch_quantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_dequantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_decode_step_quant(DecodeQArgs a, int dtype, int head_dim, int nbits, const DecodeArgs& append, hipStream_t st);
+int launch_quantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st);
+int launch_dequantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st);
+int launch_decode_step_quant_outliers(DecodeQArgs a, const DecodeOArgs& o, int dtype, int head_dim, int nbits, const DecodeArgs& append,
+                                      hipStream_t st);
 int decode_splits(int bsz, int n_q_heads, int new_rows, int rows);
 size_t decode_part_bytes(int bsz, int n_q_heads, int new_rows, int head_dim, int splits);
 int launch_sort_prefix(const RaggedSortArgs& a, int dtype, void* scratch, hipStream_t st);

@@ -8,6 +8,9 @@
 //   decode_attention_q_kernel                the hot path: decode_attention_kernel (kvc_decode.hip) over the quantized prefix,
 //                                            the quantized tail and the full-precision residual; the step's rows are
 //                                            appended by decode_append_kernel and the splits merged by decode_combine_kernel.
+// With exact outliers (KVQuant-style, `--quant_method kvquant`): the same quantize kernels with OUTL = true zero the outliers
+// before min / max and coding; outl_count_kernel / outl_scan_kernel / outl_write_kernel lay the outliers out in their pool;
+// outl_patch_kernel writes them back after dequant_kernel; decode_attention_q_kernel with OUTL = true patches them in registers.
 // The attention de-quantizes in registers, x' = fmaf(code, scale, zero), and then runs the same fp32 dot product / online
 // softmax / weighted sum as the unquantized step: its output is attention over the de-quantized cache up to the order of
 // the fp32 sums.
@@ -30,11 +33,18 @@ template <int NB> __device__ __forceinline__ uint32_t quant_code(float x, float 
     return (uint32_t)c;
 }
 
+// The split of include/kvc.h: thr is T' (already rounded to dtype); an outlier reads as +0 in the dense part.
+__device__ __forceinline__ bool is_outlier(float x, float thr) { return x < -thr || x > thr; }
+template <bool OUTL> __device__ __forceinline__ float dense(float x, float thr) {
+    if constexpr (OUTL) return is_outlier(x, thr) ? 0.0f : x;
+    return x;
+}
+
 // Keys: one wave per (b, h, group, 64 channels): lane = channel, min / max down its column over the group's rows (each row a
 // coalesced 64-element load), then per row the lane's code, OR-ed over the CPW = 32 / NB lanes of one 32-bit word by xor
 // shuffles; the word's first lane stores it.  Grid: enough 256-thread blocks for every wave item.
-template <int DT, int NB>
-__global__ __launch_bounds__(256) void quant_keys_kernel(const QuantArgs a) {
+template <int DT, int NB, bool OUTL>
+__global__ __launch_bounds__(256) void quant_keys_kernel(const QuantArgs a, const float thr) {
     typedef typename Dt<DT>::raw raw;
     constexpr int CPW = 32 / NB;
     constexpr float QMAX = (float)((1 << NB) - 1);
@@ -49,10 +59,10 @@ __global__ __launch_bounds__(256) void quant_keys_kernel(const QuantArgs a) {
     const int h = (int)(t % a.n_heads), b = (int)(t / a.n_heads);
     const int r_lo = grp * a.group, r_hi = min(a.rows, r_lo + a.group);
     const raw* src = reinterpret_cast<const raw*>(a.src) + (int64_t)b * a.s_stride_b + (int64_t)h * a.s_stride_h + ch;
-    float mn = Dt<DT>::ld(src[(int64_t)r_lo * a.s_stride_l]), mx = mn;
+    float mn = dense<OUTL>(Dt<DT>::ld(src[(int64_t)r_lo * a.s_stride_l]), thr), mx = mn;
 #pragma unroll 8
     for (int r = r_lo + 1; r < r_hi; ++r) {
-        const float x = Dt<DT>::ld(src[(int64_t)r * a.s_stride_l]);
+        const float x = dense<OUTL>(Dt<DT>::ld(src[(int64_t)r * a.s_stride_l]), thr);
         mn = x < mn ? x : mn;
         mx = x > mx ? x : mx;
     }
@@ -63,7 +73,7 @@ __global__ __launch_bounds__(256) void quant_keys_kernel(const QuantArgs a) {
     uint8_t* codes = a.codes + (int64_t)b * a.c_stride_b + (int64_t)h * a.c_stride_h + (int64_t)a.row0 * CB + (ch / CPW) * 4;
 #pragma unroll 4
     for (int r = r_lo; r < r_hi; ++r) {
-        int word = (int)(quant_code<NB>(Dt<DT>::ld(src[(int64_t)r * a.s_stride_l]), mn, sc) << ((lane % CPW) * NB));
+        int word = (int)(quant_code<NB>(dense<OUTL>(Dt<DT>::ld(src[(int64_t)r * a.s_stride_l]), thr), mn, sc) << ((lane % CPW) * NB));
 #pragma unroll
         for (int o = 1; o < CPW; o <<= 1) word |= __shfl_xor(word, o);
         if (lane % CPW == 0) *reinterpret_cast<uint32_t*>(codes + (int64_t)r * CB) = (uint32_t)word;
@@ -71,8 +81,8 @@ __global__ __launch_bounds__(256) void quant_keys_kernel(const QuantArgs a) {
 }
 
 // Values: one thread per (b, h, row, channel group): min / max along the group's G channels, then its G * NB / 32 words.
-template <int DT, int NB>
-__global__ __launch_bounds__(256) void quant_values_kernel(const QuantArgs a) {
+template <int DT, int NB, bool OUTL>
+__global__ __launch_bounds__(256) void quant_values_kernel(const QuantArgs a, const float thr) {
     typedef typename Dt<DT>::raw raw;
     constexpr int CPW = 32 / NB;
     constexpr float QMAX = (float)((1 << NB) - 1);
@@ -85,9 +95,9 @@ __global__ __launch_bounds__(256) void quant_values_kernel(const QuantArgs a) {
     t /= a.rows;
     const int h = (int)(t % a.n_heads), b = (int)(t / a.n_heads);
     const raw* src = reinterpret_cast<const raw*>(a.src) + (int64_t)b * a.s_stride_b + (int64_t)h * a.s_stride_h + (int64_t)r * a.s_stride_l + j * G;
-    float mn = Dt<DT>::ld(src[0]), mx = mn;
+    float mn = dense<OUTL>(Dt<DT>::ld(src[0]), thr), mx = mn;
     for (int e = 1; e < G; ++e) {
-        const float x = Dt<DT>::ld(src[e]);
+        const float x = dense<OUTL>(Dt<DT>::ld(src[e]), thr);
         mn = x < mn ? x : mn;
         mx = x > mx ? x : mx;
     }
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(256) void quant_values_kernel(const QuantArgs a) {
     for (int wi = 0; wi < G / CPW; ++wi) {
         uint32_t word = 0;
 #pragma unroll
-        for (int e = 0; e < CPW; ++e) word |= quant_code<NB>(Dt<DT>::ld(src[wi * CPW + e]), mn, sc) << (e * NB);
+        for (int e = 0; e < CPW; ++e) word |= quant_code<NB>(dense<OUTL>(Dt<DT>::ld(src[wi * CPW + e]), thr), mn, sc) << (e * NB);
         codes[wi] = word;
     }
 }
@@ -138,6 +148,112 @@ __global__ __launch_bounds__(256) void dequant_kernel(const QuantArgs a) {
     }
 }
 
+// ---- the sparse half: one wave per (b, h, row) of the call; lane = channel within each 64-channel chunk ----------------------
+__device__ __forceinline__ int wave_item_rows(const QuantArgs& a, int& b, int& h, int& r) {
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (int64_t)a.bsz * a.n_heads * a.rows) return 0;
+    r = (int)(item % a.rows);
+    const int64_t t = item / a.rows;
+    h = (int)(t % a.n_heads); b = (int)(t / a.n_heads);
+    return 1;
+}
+
+// The row's outlier count (ballot + popcount per chunk) into its rowinfo word, for outl_scan_kernel.
+template <int DT>
+__global__ __launch_bounds__(256) void outl_count_kernel(const QuantArgs a, const OutlArgs o) {
+    typedef typename Dt<DT>::raw raw;
+    int b, h, r;
+    if (!wave_item_rows(a, b, h, r)) return;
+    const int lane = threadIdx.x & 63;
+    const raw* src = reinterpret_cast<const raw*>(a.src) + (int64_t)b * a.s_stride_b + (int64_t)h * a.s_stride_h + (int64_t)r * a.s_stride_l;
+    uint32_t cnt = 0;
+    for (int c0 = 0; c0 < a.head_dim; c0 += 64)
+        cnt += (uint32_t)__popcll(__ballot(is_outlier(Dt<DT>::ld(src[c0 + lane]), o.thr)));
+    if (lane == 0) o.rowinfo[(int64_t)b * o.ri_stride_b + (int64_t)h * o.ri_stride_h + a.row0 + r] = cnt;
+}
+
+// One block per batch row: exclusive scan of the counts in (h, row) order from used[b]; rowinfo = (start << 8) | count for rows that
+// fit below pool_capacity, 0 otherwise; used[b] += total (saturating at INT32_MAX).
+__global__ __launch_bounds__(1024) void outl_scan_kernel(const QuantArgs a, const OutlArgs o) {
+    __shared__ int64_t sm_wave[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n = (int64_t)a.n_heads * a.rows;
+    const int64_t used0 = o.used[b];
+    uint32_t* ri = o.rowinfo + (int64_t)b * o.ri_stride_b + a.row0;
+    int64_t carry = 0;
+    for (int64_t base = 0; base < n; base += 1024) {
+        const int64_t idx = base + tid;
+        const int h = (int)(idx / a.rows), r = (int)(idx % a.rows);
+        const uint32_t cnt = idx < n ? (ri[(int64_t)h * o.ri_stride_h + r] & 0xffu) : 0u;
+        int64_t x = cnt;                                               // inclusive scan over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int64_t y = __shfl_up(x, off);
+            if (lane >= off) x += y;
+        }
+        if (lane == 63) sm_wave[wave] = x;
+        __syncthreads();
+        int64_t before = 0, total = 0;
+        for (int w = 0; w < 16; ++w) {
+            before += w < wave ? sm_wave[w] : 0;
+            total += sm_wave[w];
+        }
+        const int64_t start = used0 + carry + before + x - cnt;
+        if (idx < n)
+            ri[(int64_t)h * o.ri_stride_h + r] = (cnt > 0 && start + cnt <= o.pool_capacity) ? (uint32_t)(start << 8) | cnt : 0u;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int64_t u = used0 + carry;
+        o.used[b] = u > 0x7fffffff ? 0x7fffffff : (int32_t)u;
+    }
+}
+
+// The row's entries in channel order at its start: rank = mbcnt of the chunk's ballot + the earlier chunks' popcounts.
+template <int DT>
+__global__ __launch_bounds__(256) void outl_write_kernel(const QuantArgs a, const OutlArgs o) {
+    typedef typename Dt<DT>::raw raw;
+    int b, h, r;
+    if (!wave_item_rows(a, b, h, r)) return;
+    const int lane = threadIdx.x & 63;
+    const uint32_t word = o.rowinfo[(int64_t)b * o.ri_stride_b + (int64_t)h * o.ri_stride_h + a.row0 + r];
+    const uint32_t cnt = word & 0xffu;
+    if (cnt == 0) return;
+    const int64_t e0 = (int64_t)b * o.pool_stride_b + (word >> 8);
+    const raw* src = reinterpret_cast<const raw*>(a.src) + (int64_t)b * a.s_stride_b + (int64_t)h * a.s_stride_h + (int64_t)r * a.s_stride_l;
+    uint32_t base = 0;
+    for (int c0 = 0; c0 < a.head_dim; c0 += 64) {
+        const raw x = src[c0 + lane];
+        const bool pred = is_outlier(Dt<DT>::ld(x), o.thr);
+        const uint64_t m = __ballot(pred);
+        const uint32_t rank = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (pred && rank < cnt) {                                      // rank < cnt: never past the row's share of the pool
+            o.chan[e0 + rank] = (uint8_t)(c0 + lane);
+            reinterpret_cast<raw*>(o.val)[e0 + rank] = x;
+        }
+        base += (uint32_t)__popcll(m);
+    }
+}
+
+// After dequant_kernel: the row's outliers back at their channels of dst rows [0, rows).
+template <int DT>
+__global__ __launch_bounds__(256) void outl_patch_kernel(const QuantArgs a, const OutlArgs o) {
+    typedef typename Dt<DT>::raw raw;
+    int b, h, r;
+    if (!wave_item_rows(a, b, h, r)) return;
+    const int lane = threadIdx.x & 63;
+    const uint32_t word = o.rowinfo[(int64_t)b * o.ri_stride_b + (int64_t)h * o.ri_stride_h + a.row0 + r];
+    const uint32_t cnt = word & 0xffu, start = word >> 8;
+    if (cnt == 0 || (int64_t)start + cnt > o.pool_capacity) return;
+    const int64_t e0 = (int64_t)b * o.pool_stride_b + start;
+    raw* dst = reinterpret_cast<raw*>(a.dst) + (int64_t)b * a.s_stride_b + (int64_t)h * a.s_stride_h + (int64_t)r * a.s_stride_l;
+    for (uint32_t j = lane; j < cnt; j += 64) {
+        const int ch = o.chan[e0 + j];
+        if (ch < a.head_dim) dst[ch] = reinterpret_cast<const raw*>(o.val)[e0 + j];
+    }
+}
+
 template <int DT> __device__ __forceinline__ void widen_chunk_q(const uint4& v, float* x) {
     if constexpr (DT == KVC_FP32) {
         x[0] = u2f(v.x); x[1] = u2f(v.y); x[2] = u2f(v.z); x[3] = u2f(v.w);
@@ -151,14 +267,32 @@ template <int DT> __device__ __forceinline__ void widen_chunk_q(const uint4& v, 
     }
 }
 
+// x'' of one row's lane: entries [start, start + count) of the pool (rowinfo word), channel c * EPL + e -> element e.
+template <int DT, int EPL>
+__device__ __forceinline__ void patch_row(float* x, uint32_t word, const uint8_t* chan, const void* val, int64_t vofs, int cap, int c) {
+    typedef typename Dt<DT>::raw raw;
+    const uint32_t cnt = word & 0xffu, start = word >> 8;
+    if (cnt == 0 || (int64_t)start + cnt > cap) return;
+    const raw* vp = reinterpret_cast<const raw*>(val) + vofs + start;
+    for (uint32_t j = 0; j < cnt; ++j) {
+        const int rel = (int)chan[start + j] - c * EPL;
+        const float v = Dt<DT>::ld(vp[j]);
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) x[e] = rel == e ? v : x[e];
+    }
+}
+
 // grid = (b * H_q, new_rows, splits), block = 256 (4 waves) — decode_attention_kernel's mapping: LPR lanes share a row, lane c
 // holds channels [c * EPL, (c + 1) * EPL) of q and acc.  Rows [0, P) are the query head's quantized prefix, [P, PQ) its KV
 // head's quantized tail, [PQ, PQ + res_rows + i + 1) the residual (full precision, the step's rows included).  For a quantized row
 // a lane loads its EPL codes as one word of WB = EPL * NB / 8 bytes (instead of 16 bytes), the key (scale, zero) of its channels
 // from the row's key group, and the value (scale, zero) of its channel group; every load of an iteration is issued before the
 // first is used.
-template <int DT, int D, int NB>
-__global__ __launch_bounds__(256) void decode_attention_q_kernel(const DecodeQArgs a) {
+// OUTL: each quantized row's key and value rowinfo words are loaded with the row's other loads; for a row with entries the row's
+// lanes walk them (broadcast loads: every lane of the row reads the same entry) and select the entry's value into the element
+// whose channel matches — a predicated select over the EPL unrolled elements, never a runtime-indexed register array.
+template <int DT, int D, int NB, bool OUTL>
+__global__ __launch_bounds__(256) void decode_attention_q_kernel(const DecodeQArgs a, const DecodeOArgs o) {
     typedef typename Dt<DT>::raw raw;
     constexpr int ES = Dt<DT>::esize, EPL = 16 / ES, LPR = D / EPL;
     constexpr int RPW = 64 / LPR, RPI = 4 * RPW, UNR = 4;
@@ -201,13 +335,15 @@ __global__ __launch_bounds__(256) void decode_attention_q_kernel(const DecodeQAr
         float4 ksc[UNR][F4], kzp[UNR][F4];
         float2 vsz[UNR];
         uint4 kv[UNR], vv[UNR];
-        bool valid[UNR], quant[UNR];
+        bool valid[UNR], quant[UNR], inpre[UNR];
+        uint32_t kri[UNR], vri[UNR];
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const int r = r0 + u * RPI + wave * RPW + slot;
             valid[u] = r < r_end;
             quant[u] = r < PQ;
             const bool pre = r < P;
+            inpre[u] = pre;
             const int rr = pre ? r : r - P;                                  // row within its quantized segment
             const uint8_t* kcp = (pre ? pkc : tkc) + (int64_t)rr * CB;
             const uint8_t* vcp = (pre ? pvc : tvc) + (int64_t)rr * CB;
@@ -225,6 +361,12 @@ __global__ __launch_bounds__(256) void decode_attention_q_kernel(const DecodeQAr
             const int64_t fr = (int64_t)(r - PQ) * ROWB;
             kv[u] = lf ? reinterpret_cast<const uint4*>(kr + fr)[c] : make_uint4(0, 0, 0, 0);
             vv[u] = lf ? reinterpret_cast<const uint4*>(vr + fr)[c] : make_uint4(0, 0, 0, 0);
+            if constexpr (OUTL) {
+                const OSegArgs& os = pre ? o.pre : o.qt;
+                const int hh = pre ? h : g;
+                kri[u] = lq ? os.kri[(int64_t)b * os.kri_b + (int64_t)hh * os.kri_h + rr] : 0u;
+                vri[u] = lq ? os.vri[(int64_t)b * os.vri_b + (int64_t)hh * os.vri_h + rr] : 0u;
+            }
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
@@ -237,6 +379,11 @@ __global__ __launch_bounds__(256) void decode_attention_q_kernel(const DecodeQAr
                 for (int e = 0; e < EPL; ++e) {
                     kf[e] = __builtin_fmaf((float)((uint32_t)(kw >> (e * NB)) & MASK), ks[e], kz[e]);
                     vf[e] = __builtin_fmaf((float)((uint32_t)(vw >> (e * NB)) & MASK), vsz[u].x, vsz[u].y);
+                }
+                if constexpr (OUTL) {
+                    const OSegArgs& os = inpre[u] ? o.pre : o.qt;
+                    patch_row<DT, EPL>(kf, kri[u], os.kch + (int64_t)b * os.kpool_b, os.kval, (int64_t)b * os.kpool_b, os.kcap, c);
+                    patch_row<DT, EPL>(vf, vri[u], os.vch + (int64_t)b * os.vpool_b, os.vval, (int64_t)b * os.vpool_b, os.vcap, c);
                 }
             } else {
                 widen_chunk_q<DT>(kv[u], kf);
@@ -293,8 +440,8 @@ int launch_quantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStrea
         ? (int64_t)a.bsz * a.n_heads * ((a.rows + a.group - 1) / a.group) * (a.head_dim / 64) * 64
         : (int64_t)a.bsz * a.n_heads * a.rows * (a.head_dim / a.group);
 #define KVC_CASE(DT_, NB_) if (dtype == DT_ && nbits == NB_) { \
-        if (mode == KVC_QUANT_KEYS) hipLaunchKernelGGL((quant_keys_kernel<DT_, NB_>), dim3(blocks_for(items)), dim3(256), 0, st, a); \
-        else hipLaunchKernelGGL((quant_values_kernel<DT_, NB_>), dim3(blocks_for(items)), dim3(256), 0, st, a); return 0; }
+        if (mode == KVC_QUANT_KEYS) hipLaunchKernelGGL((quant_keys_kernel<DT_, NB_, false>), dim3(blocks_for(items)), dim3(256), 0, st, a, 0.0f); \
+        else hipLaunchKernelGGL((quant_values_kernel<DT_, NB_, false>), dim3(blocks_for(items)), dim3(256), 0, st, a, 0.0f); return 0; }
     KVC_CASE(KVC_BF16, 2) KVC_CASE(KVC_BF16, 4) KVC_CASE(KVC_BF16, 8) KVC_CASE(KVC_FP16, 2) KVC_CASE(KVC_FP16, 4) KVC_CASE(KVC_FP16, 8)
     KVC_CASE(KVC_FP32, 2) KVC_CASE(KVC_FP32, 4) KVC_CASE(KVC_FP32, 8)
 #undef KVC_CASE
@@ -323,7 +470,63 @@ int launch_decode_step_quant(DecodeQArgs a, int dtype, int head_dim, int nbits, 
     const dim3 grid((unsigned)(a.bsz * a.n_q_heads), (unsigned)a.new_rows, (unsigned)a.splits);
     int rc = KVC_ERR_UNSUPPORTED;
 #define KVC_CASE(DT_, D_, NB_) if (dtype == DT_ && head_dim == D_ && nbits == NB_) { \
-        hipLaunchKernelGGL((decode_attention_q_kernel<DT_, D_, NB_>), grid, dim3(256), 0, st, a); rc = 0; }
+        hipLaunchKernelGGL((decode_attention_q_kernel<DT_, D_, NB_, false>), grid, dim3(256), 0, st, a, DecodeOArgs{}); rc = 0; }
+    KVC_CASE(KVC_BF16, 128, 2) KVC_CASE(KVC_BF16, 128, 4) KVC_CASE(KVC_BF16, 128, 8)
+    KVC_CASE(KVC_BF16, 64, 2) KVC_CASE(KVC_BF16, 64, 4) KVC_CASE(KVC_BF16, 64, 8)
+    KVC_CASE(KVC_FP16, 128, 2) KVC_CASE(KVC_FP16, 128, 4) KVC_CASE(KVC_FP16, 128, 8)
+    KVC_CASE(KVC_FP16, 64, 2) KVC_CASE(KVC_FP16, 64, 4) KVC_CASE(KVC_FP16, 64, 8)
+    KVC_CASE(KVC_FP32, 128, 2) KVC_CASE(KVC_FP32, 128, 4) KVC_CASE(KVC_FP32, 128, 8)
+    KVC_CASE(KVC_FP32, 64, 2) KVC_CASE(KVC_FP32, 64, 4) KVC_CASE(KVC_FP32, 64, 8)
+#undef KVC_CASE
+    if (rc) return rc;
+    if (a.splits > 1) {
+        DecodeArgs cmb = append;
+        cmb.part = a.part; cmb.splits = a.splits;
+        return launch_decode_combine(cmb, dtype, head_dim, st);
+    }
+    return 0;
+}
+
+int launch_quantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st) {
+    if (a.rows <= 0) return 0;
+    const int64_t items = mode == KVC_QUANT_KEYS
+        ? (int64_t)a.bsz * a.n_heads * ((a.rows + a.group - 1) / a.group) * (a.head_dim / 64) * 64
+        : (int64_t)a.bsz * a.n_heads * a.rows * (a.head_dim / a.group);
+    const unsigned row_waves = blocks_for((int64_t)a.bsz * a.n_heads * a.rows * 64);
+    int rc = KVC_ERR_UNSUPPORTED;
+#define KVC_CASE(DT_, NB_) if (dtype == DT_ && nbits == NB_) { \
+        if (mode == KVC_QUANT_KEYS) hipLaunchKernelGGL((quant_keys_kernel<DT_, NB_, true>), dim3(blocks_for(items)), dim3(256), 0, st, a, o.thr); \
+        else hipLaunchKernelGGL((quant_values_kernel<DT_, NB_, true>), dim3(blocks_for(items)), dim3(256), 0, st, a, o.thr); \
+        hipLaunchKernelGGL((outl_count_kernel<DT_>), dim3(row_waves), dim3(256), 0, st, a, o); \
+        hipLaunchKernelGGL(outl_scan_kernel, dim3((unsigned)a.bsz), dim3(1024), 0, st, a, o); \
+        hipLaunchKernelGGL((outl_write_kernel<DT_>), dim3(row_waves), dim3(256), 0, st, a, o); rc = 0; }
+    KVC_CASE(KVC_BF16, 2) KVC_CASE(KVC_BF16, 4) KVC_CASE(KVC_BF16, 8) KVC_CASE(KVC_FP16, 2) KVC_CASE(KVC_FP16, 4) KVC_CASE(KVC_FP16, 8)
+    KVC_CASE(KVC_FP32, 2) KVC_CASE(KVC_FP32, 4) KVC_CASE(KVC_FP32, 8)
+#undef KVC_CASE
+    return rc;
+}
+
+int launch_dequantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st) {
+    if (a.rows <= 0) return 0;
+    if (int rc = launch_dequantize(a, dtype, nbits, mode, st)) return rc;
+    const unsigned row_waves = blocks_for((int64_t)a.bsz * a.n_heads * a.rows * 64);
+    if (dtype == KVC_BF16) hipLaunchKernelGGL((outl_patch_kernel<KVC_BF16>), dim3(row_waves), dim3(256), 0, st, a, o);
+    else if (dtype == KVC_FP16) hipLaunchKernelGGL((outl_patch_kernel<KVC_FP16>), dim3(row_waves), dim3(256), 0, st, a, o);
+    else hipLaunchKernelGGL((outl_patch_kernel<KVC_FP32>), dim3(row_waves), dim3(256), 0, st, a, o);
+    return 0;
+}
+
+int launch_decode_step_quant_outliers(DecodeQArgs a, const DecodeOArgs& o, int dtype, int head_dim, int nbits, const DecodeArgs& append,
+                                      hipStream_t st) {
+    launch_decode_append(append, st);
+    const int rows = a.pre.rows + a.qt.rows + a.res_rows + a.new_rows;
+    if (a.splits < 1 || a.part == nullptr) a.splits = 1;
+    a.rows_per_split = a.splits == 1 ? rows : ((rows + a.splits - 1) / a.splits + 63) / 64 * 64;
+    if (a.splits > 1) a.splits = (rows + a.rows_per_split - 1) / a.rows_per_split;          // the same splits as the KIVI step
+    const dim3 grid((unsigned)(a.bsz * a.n_q_heads), (unsigned)a.new_rows, (unsigned)a.splits);
+    int rc = KVC_ERR_UNSUPPORTED;
+#define KVC_CASE(DT_, D_, NB_) if (dtype == DT_ && head_dim == D_ && nbits == NB_) { \
+        hipLaunchKernelGGL((decode_attention_q_kernel<DT_, D_, NB_, true>), grid, dim3(256), 0, st, a, o); rc = 0; }
     KVC_CASE(KVC_BF16, 128, 2) KVC_CASE(KVC_BF16, 128, 4) KVC_CASE(KVC_BF16, 128, 8)
     KVC_CASE(KVC_BF16, 64, 2) KVC_CASE(KVC_BF16, 64, 4) KVC_CASE(KVC_BF16, 64, 8)
     KVC_CASE(KVC_FP16, 128, 2) KVC_CASE(KVC_FP16, 128, 4) KVC_CASE(KVC_FP16, 128, 8)
