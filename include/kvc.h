@@ -234,6 +234,39 @@ int kvc_decode_step2(const kvc_decode_params* p, const kvc_decode_ext* ext /* nu
                      const void* k_pruned /* nullable */, const int16_t* chan /* nullable */, void* out,
                      void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
 
+/* ---- decode-stage compression: re-compress the SPLIT decode cache in place (the reference's README TODO "Support KV cache
+ * compression at decoding stage") ---------------------------------------------------------------------------------------------
+ * The cache of one layer is the prefix [b][H_q][P][D] (per query head) and the tail [b][H_kv][T][D] (per KV head, the decoded
+ * rows kvc_decode_step appended).  With G = n_q_heads / n_kv_heads and L = P + T, the call computes EXACTLY what kvc_compress
+ * computes (dot_mode EXACT, this tie_mode) for
+ *     K[b][h][r] = r < P ? k_prefix[b][h][r] : k_tail[b][h / G][r - P]      (and V alike), r in [0, L), n_kv_heads = H_q,
+ *     query rows L-W .. L-1 = the W rows of the query ring, window row w at ring row (ring_start + w) % W,
+ *     p->k rows kept besides the W window rows,
+ * without materialising K: k_out / v_out [b][H_q][k + W][D] receive cat(K[idx], K[L-W:L]) — the last W rows always come from
+ * the tail (T >= W) — idx_out [b][H_q][k] int64 the indices in this virtual row numbering, scores_out [b][H_q][L-W] dtype the
+ * pooled scores (both nullable; StreamingLLM: idx = arange(k), idx_out must be NULL, scores_out is not written).
+ * Stages: a two-segment window scan (the d-ascending fp32 fmaf chain, the reference's three roundings and the local causal
+ * mask), kvc_compress's softmax / pooling stage, its selection, and a two-source gather.  dot_mode mfma16 does not apply here.
+ * Limits: those of kvc_compress (head_dim 64 / 128, W <= 64, odd kernel_size <= 63, 0 <= k <= L - W, L > W, tie-mode limits),
+ * T >= W, every pointer and stride 16-byte aligned, and k_out / v_out disjoint from each other, the prefix and the tail (the
+ * output never aliases the input: a caller alternates two prefix buffers).  Enqueue-only: no allocation, no synchronisation.
+ * Workspace: kvc_decode_compress_workspace_bytes(p) bytes, 256-byte aligned (0 for StreamingLLM). */
+typedef struct kvc_decode_compress_params {
+    int32_t method;                 /* KVC_SNAPKV, KVC_PYRAMIDKV or KVC_STREAMINGLLM */
+    int32_t dtype, bsz, n_q_heads, n_kv_heads, head_dim;
+    int32_t prefix_rows, tail_rows; /* P (per query head), T >= window (per KV head); L = P + T */
+    int32_t window, k, kernel_size, pooling, tie_mode;
+    int32_t ring_start;             /* window row w is ring row (ring_start + w) % window */
+    int64_t ring_stride_b, ring_stride_h;           /* q ring [b][h_q][window][D], rows dense */
+    int64_t prefix_stride_b, prefix_stride_h;       /* k_prefix / v_prefix [b][h_q][row][D] */
+    int64_t tail_stride_b, tail_stride_h;           /* k_tail / v_tail [b][h_kv][row][D] */
+    int64_t out_stride_b, out_stride_h;             /* k_out / v_out [b][h_q][row][D] */
+} kvc_decode_compress_params;
+size_t kvc_decode_compress_workspace_bytes(const kvc_decode_compress_params* p);
+int kvc_decode_compress(const kvc_decode_compress_params* p, const void* q_ring, const void* k_prefix, const void* v_prefix,
+                        const void* k_tail, const void* v_tail, void* k_out, void* v_out, int64_t* idx_out /* nullable */,
+                        void* scores_out /* nullable */, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- quantized decode cache (KIVI-style, --quant_method kivi --nbits N of the reference's run scripts) ----------------------
  * Rule: asymmetric round-to-nearest, every group on its own in fp32 with the inputs widened exactly.  KEYS are grouped per
  * channel (G = group_size consecutive stored rows share one (scale, zero) per channel; a segment whose rows are not a multiple

@@ -9,11 +9,12 @@ All compute runs in hand-written HIP kernels (csrc/, libkvc_hip.so) through the 
 there is no CPU or eager-PyTorch fallback: if the extension is missing the import of `_kvc` raises.
 """
 __version__ = "0.1.0"
-__all__ = ["QuantizedCompressedCache", "QuantizedCompressedLayer", "KVQuantCompressedCache", "KVQuantCompressedLayer"]
+__all__ = ["QuantizedCompressedCache", "QuantizedCompressedLayer", "KVQuantCompressedCache", "KVQuantCompressedLayer",
+           "DecodeCompressedCache", "DecodeCompressedLayer"]
 
 
 def __getattr__(name):
-    # the quantized decode cache (cache.py) is exported lazily: importing the package does not import transformers
+    # the quantized and decode-compressed caches (cache.py) are exported lazily: importing the package does not import transformers
     if name in __all__:
         from . import cache
         return getattr(cache, name)

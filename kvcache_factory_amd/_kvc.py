@@ -29,7 +29,8 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_merge_workspace_bytes", "kvc_merge_pivot", "kvc_think_prune", "kvc_decode_workspace_bytes", "kvc_decode_step2",
            "kvc_cam_workspace_bytes", "kvc_cam_plan", "kvc_cam_merge", "kvc_quantize_rows", "kvc_dequantize_rows",
            "kvc_decode_quant_workspace_bytes", "kvc_decode_step_quant", "kvc_quantize_rows_outliers",
-           "kvc_dequantize_rows_outliers", "kvc_decode_quant_outliers_workspace_bytes", "kvc_decode_step_quant_outliers")
+           "kvc_dequantize_rows_outliers", "kvc_decode_quant_outliers_workspace_bytes", "kvc_decode_step_quant_outliers",
+           "kvc_decode_compress_workspace_bytes", "kvc_decode_compress")
 
 
 class KvcError(RuntimeError):
@@ -100,6 +101,13 @@ class QuantOutliers(ctypes.Structure):
         (n, ctypes.c_int64) for n in ("pool_stride_b", "rowinfo_stride_b", "rowinfo_stride_h")]
 
 
+class DecodeCompressParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("method", "dtype", "bsz", "n_q_heads", "n_kv_heads", "head_dim", "prefix_rows", "tail_rows",
+                                               "window", "k", "kernel_size", "pooling", "tie_mode", "ring_start")] + [
+        (n, ctypes.c_int64) for n in ("ring_stride_b", "ring_stride_h", "prefix_stride_b", "prefix_stride_h", "tail_stride_b",
+                                      "tail_stride_h", "out_stride_b", "out_stride_h")]
+
+
 _lib = None
 
 
@@ -161,6 +169,10 @@ def lib():
         L.kvc_decode_quant_outliers_workspace_bytes.argtypes = [dq, qs, qs, qo, qo]
         L.kvc_decode_quant_outliers_workspace_bytes.restype = sz
         L.kvc_decode_step_quant_outliers.argtypes = [dq, qs, qs, qo, qo] + [vp] * 7 + [sz, vp]
+        dc = ctypes.POINTER(DecodeCompressParams)
+        L.kvc_decode_compress_workspace_bytes.argtypes = [dc]
+        L.kvc_decode_compress_workspace_bytes.restype = sz
+        L.kvc_decode_compress.argtypes = [dc] + [vp] * 10 + [sz, vp]
         _lib = L
     return _lib
 
@@ -402,6 +414,68 @@ def decode_step(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail
                  _ptr(v_prefix), _ptr(k_tail), _ptr(v_tail), _ptr(k_pruned if pruned_rows else None), _ptr(chan if pruned_rows else None),
                  _ptr(out), _ptr(ws), nbytes, _stream(dev)))
     return out
+
+
+def decode_compress_params(method, ring, k_prefix, prefix_rows, k_tail, tail_rows, out, window, n_keep, kernel_size=5,
+                           pooling="avgpool", tie_mode="torch_cpu", ring_start=0):
+    """kvc_decode_compress_params of one call (tensors only describe shapes and strides; nothing is read)."""
+    p = DecodeCompressParams()
+    b, hkv, _, D = k_tail.shape
+    p.method, p.dtype, p.bsz, p.n_kv_heads, p.head_dim = method, DTYPES[k_tail.dtype], b, hkv, D
+    p.n_q_heads = out.shape[1]
+    p.prefix_rows, p.tail_rows, p.window, p.k = prefix_rows, tail_rows, window, n_keep
+    scoring = method != STREAMINGLLM
+    p.kernel_size = kernel_size
+    if scoring and pooling not in POOLINGS:
+        raise ValueError('Pooling method not supported')      # pyramidkv_utils.py:333
+    p.pooling = POOLINGS[pooling] if scoring else POOL_NONE
+    p.tie_mode = TIE_MODES[tie_mode] if isinstance(tie_mode, str) else tie_mode
+    p.ring_start = ring_start
+    if ring is not None:
+        p.ring_stride_b, p.ring_stride_h = ring.stride(0), ring.stride(1)
+    if k_prefix is not None:
+        p.prefix_stride_b, p.prefix_stride_h = k_prefix.stride(0), k_prefix.stride(1)
+    p.tail_stride_b, p.tail_stride_h = k_tail.stride(0), k_tail.stride(1)
+    p.out_stride_b, p.out_stride_h = out.stride(0), out.stride(1)
+    return p
+
+
+def decode_compress(method, ring, ring_start, k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_rows, out, window, n_keep,
+                    kernel_size=5, pooling="avgpool", tie_mode="torch_cpu", return_indices=False, return_scores=False):
+    """kvc_decode_compress: the SPLIT decode cache of one layer — prefix [b, H_q, >= prefix_rows, D] and tail [b, H_kv, >= tail_rows,
+    D], rows dense — compressed as kvc_compress would compress cat(prefix, repeat_kv(tail)) scored by the W query rows of `ring`
+    [b, H_q, W, D] (window row w = ring row (ring_start + w) % W).  out = (k_buf, v_buf) [b, H_q, >= n_keep + W, D], disjoint
+    from the inputs, receives the n_keep + W kept rows per head.  Returns views (k_out, v_out[, idx][, scores]).
+    dot_mode is always EXACT here (mfma16 does not apply at decode time)."""
+    _require_gpu(ring, k_prefix, v_prefix, k_tail, v_tail, *out)
+    dev = _one_device(ring, k_prefix, v_prefix, k_tail, v_tail, *out)
+    kb, vb = out
+    assert kb.shape == vb.shape and kb.stride() == vb.stride() and k_tail.stride() == v_tail.stride()
+    if k_prefix is not None:
+        assert k_prefix.stride() == v_prefix.stride()
+    for t in (ring, k_prefix, k_tail, kb):
+        if t is not None:
+            assert t.stride(3) == 1 and t.stride(2) == t.shape[3], "rows must be dense"
+    scoring = method != STREAMINGLLM
+    p = decode_compress_params(method, ring if scoring else None, k_prefix, prefix_rows, k_tail, tail_rows, kb, window, n_keep,
+                               kernel_size, pooling, tie_mode, ring_start)
+    b, hq, L = kb.shape[0], kb.shape[1], prefix_rows + tail_rows
+    idx = torch.empty(b, hq, n_keep, dtype=torch.int64, device=dev) if (return_indices and scoring) else None
+    sc = torch.empty(b, hq, L - window, dtype=kb.dtype, device=dev) if (return_scores and scoring) else None
+    L_ = lib()
+    nbytes = L_.kvc_decode_compress_workspace_bytes(ctypes.byref(p))    # 0 for invalid params: the call below names the error
+    ws = workspace(dev, nbytes) if nbytes else None
+    _check(_call(dev, L_.kvc_decode_compress, ctypes.byref(p), _ptr(ring if scoring else None), _ptr(k_prefix if prefix_rows else None),
+                 _ptr(v_prefix if prefix_rows else None), _ptr(k_tail), _ptr(v_tail), _ptr(kb), _ptr(vb), _ptr(idx), _ptr(sc), _ptr(ws),
+                 nbytes, _stream(dev)))
+    res = [kb[:, :, :n_keep + window], vb[:, :, :n_keep + window]]
+    if return_indices:
+        if not scoring:
+            idx = torch.arange(n_keep, device=dev).expand(b, hq, n_keep).contiguous()
+        res.append(idx)
+    if return_scores:
+        res.append(sc)
+    return tuple(res)
 
 
 QUANT_KEYS, QUANT_VALUES = 0, 1

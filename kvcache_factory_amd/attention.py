@@ -25,7 +25,8 @@ import torch
 from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
 
 from . import pyramidkv_utils as pu
-from .cache import CompressedDynamicLayer, QuantizedCompressedCache, RaggedDynamicLayer, ThinkDynamicLayer
+from .cache import DECODE_METHODS, CompressedDynamicLayer, DecodeCompressedCache, QuantizedCompressedCache, RaggedDynamicLayer, \
+    ThinkDynamicLayer
 
 _INIT = {
     "pyramidkv": lambda self: pu.init_pyramidkv(self, num_hidden_layers=self.config.num_hidden_layers),
@@ -82,6 +83,18 @@ def _refuse_quantized(cache, method):
                                   "the SnapKV / PyramidKV / H2O / StreamingLLM / L2Norm / CAM / fullkv paths only")
 
 
+def _refuse_decode_compressed(cache, method, cluster=None):
+    """DecodeCompressedCache has a decode-time rule for SnapKV, PyramidKV and StreamingLLM only (and not with the pivot merge)."""
+    if not isinstance(cache, DecodeCompressedCache):
+        return
+    if method not in DECODE_METHODS:
+        raise NotImplementedError(f"kvcache_factory_amd: {method} has no decode-time compression rule here; DecodeCompressedCache is "
+                                  "built for the snapkv / pyramidkv / streamingllm paths only")
+    if cluster is not None and getattr(cluster, "merge", None) is not None:
+        raise NotImplementedError(f"kvcache_factory_amd: {method} with merge={cluster.merge!r} has no decode-time compression rule "
+                                  "here; DecodeCompressedCache needs merge=None")
+
+
 def _pending_for(cache):
     """The prompt's PrefillBatch, kept on the cache object (one per generation)."""
     pending = getattr(cache, "_kvc_pending", None)
@@ -95,6 +108,7 @@ def make_forward(method, apply_rotary_pos_emb, eager_attention_forward, repeat_k
 
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
         init(self)
+        _refuse_decode_compressed(past_key_values, method, self.kv_cluster)
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)
         query_states = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)
@@ -104,6 +118,7 @@ def make_forward(method, apply_rotary_pos_emb, eager_attention_forward, repeat_k
         query_states, key_states = apply_rotary_pos_emb(query_states, key_states, cos, sin)
 
         attn_module = self
+        decoding = False
         if past_key_values is not None:
             layer = _layer_for(past_key_values, self.layer_idx)
             pending = _pending_for(past_key_values)
@@ -140,12 +155,14 @@ def make_forward(method, apply_rotary_pos_emb, eager_attention_forward, repeat_k
                     # N1: the step's K/V rows go to the layer's shared tail (once per KV head) and ONE kernel attends over
                     # prefix + tail — no repeat_kv, no copy of the cache (reference: llama_model.py:287-289, 306-313)
                     attn_output = layer.decode_attend(query_states, key_states, value_states, self.scaling)
+                    layer.after_decode(self.kv_cluster, query_states)           # decode-stage compression, if the layer does it
                     attn_output = attn_output.reshape(*input_shape, -1)
                     return self.o_proj(attn_output), None
                 key_states = repeat_kv(key_states, self.num_key_value_groups)
                 value_states = repeat_kv(value_states, self.num_key_value_groups)
                 key_states, value_states = past_key_values.update(key_states, value_states, self.layer_idx)
                 attn_module = _OneGroup(self)
+                decoding = True
                 # transformers builds ONE mask per forward from the first layer's lengths; layers store different numbers
                 # of tokens (PyramidKV) and eager attention no longer cuts the mask to the keys: keep its last kv columns
                 # (the new tokens' causal block sits at the end; every stored prefix token is visible to a decode step)
@@ -162,6 +179,8 @@ def make_forward(method, apply_rotary_pos_emb, eager_attention_forward, repeat_k
         attn_output, attn_weights = attention_interface(
             attn_module, query_states, key_states, value_states, attention_mask,
             dropout=0.0 if not self.training else self.attention_dropout, scaling=self.scaling, **extra, **kwargs)
+        if decoding:
+            layer.after_decode(self.kv_cluster, query_states)                   # decode-stage compression, if the layer does it
         attn_output = attn_output.reshape(*input_shape, -1).contiguous()
         attn_output = self.o_proj(attn_output)
         return attn_output, attn_weights
@@ -180,6 +199,7 @@ def make_ragged_forward(method, apply_rotary_pos_emb, eager_attention_forward, r
 
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
         _refuse_quantized(past_key_values, method)
+        _refuse_decode_compressed(past_key_values, method)
         init(self)
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)
@@ -226,6 +246,7 @@ def make_think_forward(apply_rotary_pos_emb, eager_attention_forward, repeat_kv)
 
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
         _refuse_quantized(past_key_values, "think")
+        _refuse_decode_compressed(past_key_values, "think")
         pu.init_think(self)
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)

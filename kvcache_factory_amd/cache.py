@@ -214,6 +214,174 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         # the mask must be as wide as what attention will really see: stored tokens + the new ones
         return self.stored_length() + query_length, 0
 
+    def after_decode(self, cluster, query_states):
+        """Called by the patched forwards after a decode step's attention; nothing to do unless the layer compresses at decode."""
+
+
+def _check_interval(interval):
+    if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+        raise ValueError(f"interval must be an int >= 1, got {interval!r}")
+
+
+DECODE_METHODS = ("snapkv", "pyramidkv", "streamingllm")   # the patched forwards that have a decode-time rule
+
+
+class DecodeCompressedLayer(CompressedDynamicLayer):
+    """A CompressedDynamicLayer whose decoded rows are compressed again, so that the layer stays bounded during long generations.
+
+    Budget B (fixed per layer and prompt, from the prefill's knobs): SnapKV / StreamingLLM max_capacity_prompt; PyramidKV
+    cluster._budget(2 * max_capacity_prompt) + W, the layer's pyramid budget for a prompt long enough to take the per-layer branch.
+    After every decode step (attention included) the layer holds S = P + T rows, P per query head (the prefix) and T decoded rows
+    since the last compression.  When S >= B + interval and T >= W, the S rows are replaced by the B rows kvc_compress (dot_mode
+    EXACT, the current TIE_MODE) keeps of them, scored by the post-RoPE queries of the last W decoded rows, with k = B - W and
+    the cluster's kernel_size / pooling; the step's own attention has already seen all S rows, as a prefill's attention sees
+    the whole prompt.  `true_length` keeps counting every token; get_mask_sizes reports the rows really stored.
+
+    SPLIT form (the fused step): kvc_decode_compress reads prefix and tail where they are and writes the B rows into the other
+    of two prefix buffers of exactly B rows (the prefill's buffer is dropped at the first compression); the tail buffer is
+    reused.  EXPANDED form (update: bsz > 1, beams, output_attentions, DECODE_KERNEL = 0): kvc_compress_batch with dot_mode
+    EXACT over the [b, H_q, S, D] buffer into the other buffer.  The queries live in a ring [b, H_q, W, D]: decoded row r at
+    slot r % W, written only by steps that end with S > B + interval - W (the only rows a next window can hold); StreamingLLM
+    needs none.  Nothing on this path copies from the device to the host: the trigger is host
+    arithmetic on the lengths the layer tracks.  KVC_DOT_MODE = mfma16 does not apply here."""
+
+    def __init__(self, interval=128):
+        _check_interval(interval)
+        super().__init__()
+        self.interval = interval
+        self._kalt = self._valt = None      # the other prefix buffers [b, H_q, capacity, D]: compressions alternate between the two
+        self._clear_decode()
+
+    def _clear_decode(self):
+        self._qring = None                  # post-RoPE queries [b, H_q, W, D] of the decoded rows, row r at slot r % W
+        self._p0 = self._stored             # rows of the prefix (the rest of an EXPANDED buffer are decoded rows)
+        self._plan = None                   # (method, B, W) of this prompt, set at its first decode step
+        self.compressions = 0
+
+    _batch_tensors = CompressedDynamicLayer._batch_tensors + ("_kalt", "_valt", "_qring")
+
+    def reset(self):
+        super().reset()
+        self._kalt = self._valt = None
+        self._clear_decode()
+
+    def prefill(self, k_compressed, v_compressed, true_length):
+        super().prefill(k_compressed, v_compressed, true_length)
+        self._clear_decode()
+
+    def update(self, key_states, value_states, *args, **kwargs):
+        if self._kbuf is None:
+            raise NotImplementedError("kvcache_factory_amd: DecodeCompressedCache needs a model patched with snapkv, pyramidkv or "
+                                      "streamingllm (this layer never went through a compressing prefill, e.g. fullkv)")
+        return super().update(key_states, value_states, *args, **kwargs)
+
+    def rows(self):
+        """(P, T): prefix rows per query head and decoded rows since the prefill or the last compression."""
+        if self._split:
+            return self._stored, self._tail
+        return self._p0, self._stored - self._p0
+
+    def budget(self, cluster):
+        """(method, B, W) of this layer for `cluster` (the patched forward's kv_cluster)."""
+        from . import _kvc
+        W = cluster.window_size
+        method = cluster._method
+        if method not in (_kvc.SNAPKV, _kvc.PYRAMIDKV, _kvc.STREAMINGLLM) or getattr(cluster, "merge", None) is not None:
+            raise NotImplementedError(f"kvcache_factory_amd: DecodeCompressedCache has no decode-time rule for {type(cluster).__name__}"
+                                      f" (merge={getattr(cluster, 'merge', None)!r})")
+        if self.interval < W:
+            raise ValueError(f"DecodeCompressedCache: interval {self.interval} must be >= window_size {W}")
+        if method == _kvc.PYRAMIDKV:
+            return method, cluster._budget(2 * cluster.max_capacity_prompt) + W, W
+        return method, cluster.max_capacity_prompt, W
+
+    def after_decode(self, cluster, query_states):
+        from . import _kvc
+        if self._plan is None:
+            self._plan = self.budget(cluster)
+        method, B, W = self._plan
+        P, T = self.rows()
+        S, t = P + T, query_states.shape[-2]
+        if method != _kvc.STREAMINGLLM and S > B + self.interval - W:
+            self._ring_write(query_states, S - t, W)
+        if S >= B + self.interval and T >= W:
+            self._compress(cluster, method, B, W, P, T)
+
+    def _ring_write(self, q, r0, W):
+        """Query rows r0 .. r0 + t - 1 of this step into slots r % W (only the last W of them can matter)."""
+        b, h, t, d = q.shape
+        if self._qring is None or self._qring.shape != (b, h, W, d) or self._qring.dtype != q.dtype:
+            self._qring = torch.empty(b, h, W, d, dtype=q.dtype, device=q.device)
+        m = min(t, W)
+        r0, q = r0 + t - m, q[:, :, t - m:]
+        s0 = r0 % W
+        n1 = min(m, W - s0)
+        self._qring[:, :, s0:s0 + n1].copy_(q[:, :, :n1])
+        if m > n1:
+            self._qring[:, :, :m - n1].copy_(q[:, :, n1:])
+
+    def _fits(self, t, rows):
+        """t is a whole allocation of exactly [b, H_q, rows, D] in the cache's dtype: it may serve as an alternate prefix buffer."""
+        kb = self._kbuf
+        return t is not None and t.shape == (kb.shape[0], kb.shape[1], rows, kb.shape[3]) and t.dtype == kb.dtype and \
+            t.device == kb.device and t.untyped_storage().nbytes() == t.numel() * t.element_size()
+
+    def _alt(self, rows):
+        """The other prefix buffers: exactly `rows` rows per head (B in the SPLIT form, B + interval + RESERVE in the EXPANDED one)."""
+        if not (self._fits(self._kalt, rows) and self._fits(self._valt, rows)):
+            kb = self._kbuf
+            self._kalt = self._valt = None                                # (released before the new pair is allocated)
+            self._kalt = torch.empty(kb.shape[0], kb.shape[1], rows, kb.shape[3], dtype=kb.dtype, device=kb.device)
+            self._valt = torch.empty_like(self._kalt)
+        return self._kalt, self._valt
+
+    def _compress(self, cluster, method, B, W, P, T):
+        from . import _kvc
+        from . import pyramidkv_utils as pu
+        S, k = P + T, B - W
+        scoring = method != _kvc.STREAMINGLLM
+        ring_start = S % W
+        rows = B if self._split else B + self.interval + self.RESERVE      # the EXPANDED form appends behind the prefix
+        if self._split:
+            kout, vout = self._alt(rows)
+            _kvc.decode_compress(method, self._qring if scoring else None, ring_start, self._kbuf, self._vbuf, P, self._ktail, self._vtail,
+                                 T, (kout, vout), W, k, cluster.kernel_size, cluster.pooling, pu.TIE_MODE)
+            self._tail = 0
+        else:
+            kout, vout = self._alt(rows)
+            q = None
+            if scoring:
+                q = self._qring if ring_start == 0 else torch.roll(self._qring, -ring_start, dims=2)   # chronological order
+            _kvc.compress_batch(method, [q] if scoring else None, [self._kbuf[:, :, :S]], [self._vbuf[:, :, :S]], W, [k],
+                                cluster.kernel_size, cluster.pooling if scoring else None, pu.TIE_MODE,
+                                q_rows="window" if scoring else "all", n_q_heads=self._kbuf.shape[1], outs=[(kout, vout)], reuse=True,
+                                dot_mode="exact")                 # the rule is EXACT whatever KVC_DOT_MODE says
+        old_k, old_v = self._kbuf, self._vbuf
+        self._kbuf, self._vbuf = kout, vout
+        # the buffers compressed from become the next alternate only if they have exactly the size this form needs; the
+        # prefill's (spare rows, or a view into a slab shared by a group of layers) is dropped here
+        keep = self._fits(old_k, rows) and self._fits(old_v, rows)
+        self._kalt, self._valt = (old_k, old_v) if keep else (None, None)
+        self._stored = self._p0 = B
+        self.compressions += 1
+
+
+class DecodeCompressedCache(Cache):
+    """A transformers Cache of DecodeCompressedLayer, one per hidden layer: the prompt is compressed at prefill as usual, and
+    every `interval` decoded tokens each layer is compressed again to its budget, so that memory and per-step attention stay
+    bounded during long generations (the reference's README TODO "Support KV cache compression at decoding stage").
+
+        model.generate(ids, past_key_values=DecodeCompressedCache(model.config, interval=128))
+
+    Works with the snapkv, pyramidkv and streamingllm patches; the rule is DecodeCompressedLayer's.  Other methods, merge="pivot"
+    and an unpatched model (fullkv) refuse it with NotImplementedError.  interval must be >= the config's window_size."""
+
+    def __init__(self, config, interval=128):
+        _check_interval(interval)
+        text = config.get_text_config() if hasattr(config, "get_text_config") else config
+        self.interval = interval
+        super().__init__(layers=[DecodeCompressedLayer(interval) for _ in range(text.num_hidden_layers)])
+
 
 def _check_quant_args(nbits, q_group_size, residual_length):
     if nbits not in (2, 4, 8):

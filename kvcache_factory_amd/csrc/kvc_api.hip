@@ -1307,3 +1307,191 @@ __attribute__((visibility("default"))) int kvc_compress_batch(const kvc_params* 
 }
 
 }  // extern "C"
+
+// ---- decode-stage compression (kvc_decode_compress.hip) ----------------------------------------------------------------------
+namespace {
+
+inline bool dc_scoring(int method) { return method == KVC_SNAPKV || method == KVC_PYRAMIDKV; }
+
+int dc_strides(const char* what, int es, int64_t sb, int64_t sh, int64_t rows, int heads, int head_dim) {
+    if ((sb * es) % 16 || (sh * es) % 16) return fail(KVC_ERR_ALIGNMENT, "%s strides not multiples of 16 bytes", what);
+    if (sh < rows * head_dim || sb < (int64_t)heads * sh)
+        return fail(KVC_ERR_INVALID, "%s strides (%lld, %lld) smaller than its [heads=%d][rows=%lld][head_dim=%d] extent", what, (long long)sb,
+                    (long long)sh, heads, (long long)rows, head_dim);
+    return KVC_OK;
+}
+
+// Every field of the params, before any pointer is looked at.
+int dc_check(const kvc_decode_compress_params* p) {
+    if (!p) return fail(KVC_ERR_INVALID, "params is NULL");
+    if (p->method != KVC_SNAPKV && p->method != KVC_PYRAMIDKV && p->method != KVC_STREAMINGLLM)
+        return fail(KVC_ERR_INVALID, "decode compression: method %d is not SnapKV, PyramidKV or StreamingLLM", p->method);
+    if (p->dtype < KVC_BF16 || p->dtype > KVC_FP32) return fail(KVC_ERR_INVALID, "unknown dtype %d", p->dtype);
+    if (p->bsz < 1 || p->n_q_heads < 1 || p->n_kv_heads < 1) return fail(KVC_ERR_INVALID, "bsz / head counts must be positive");
+    if (p->n_q_heads % p->n_kv_heads) return fail(KVC_ERR_INVALID, "n_q_heads %d not a multiple of n_kv_heads %d", p->n_q_heads, p->n_kv_heads);
+    if (p->head_dim != 64 && p->head_dim != 128) return fail(KVC_ERR_UNSUPPORTED, "decode compression is built for head_dim 64 and 128, got %d", p->head_dim);
+    if (p->window < 1) return fail(KVC_ERR_INVALID, "window must be >= 1");
+    if (p->window > 64) return fail(KVC_ERR_UNSUPPORTED, "scoring window %d > 64 not built", p->window);
+    if (p->prefix_rows < 0) return fail(KVC_ERR_INVALID, "prefix_rows %d must be >= 0", p->prefix_rows);
+    if (p->tail_rows < p->window) return fail(KVC_ERR_INVALID, "tail_rows %d < window %d: the window rows come from the tail", p->tail_rows, p->window);
+    const int64_t L = (int64_t)p->prefix_rows + p->tail_rows;
+    if (L > 0x7fffffffLL) return fail(KVC_ERR_INVALID, "prefix_rows + tail_rows overflows int32");
+    if (L <= p->window) return fail(KVC_ERR_INVALID, "q_len %lld must exceed window %d", (long long)L, p->window);
+    if (p->k < 0 || p->k > L - p->window)
+        return fail(KVC_ERR_INVALID, "k=%d outside [0, q_len-window=%lld] (reference: topk k out of range)", p->k, (long long)(L - p->window));
+    if (p->tie_mode != KVC_TIES_TORCH_CPU && p->tie_mode != KVC_TIES_CANONICAL) return fail(KVC_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
+    const int es = esize_of(p->dtype), D = p->head_dim;
+    if (dc_scoring(p->method)) {
+        if (p->pooling != KVC_POOL_AVG && p->pooling != KVC_POOL_MAX && p->pooling != KVC_POOL_NONE)
+            return fail(KVC_ERR_INVALID, "Pooling method not supported");
+        if (p->pooling != KVC_POOL_NONE) {
+            if (p->kernel_size < 1 || p->kernel_size > 63) return fail(KVC_ERR_UNSUPPORTED, "kernel_size %d outside [1,63]", p->kernel_size);
+            if ((p->kernel_size & 1) == 0)
+                return fail(KVC_ERR_UNSUPPORTED, "even kernel_size %d: the reference's pooled length becomes n+1 and its gather can index out of range", p->kernel_size);
+        }
+        if (p->ring_start < 0 || p->ring_start >= p->window) return fail(KVC_ERR_INVALID, "ring_start %d outside [0, window=%d)", p->ring_start, p->window);
+        const int64_t n_sel = L - p->window;
+        if (p->tie_mode == KVC_TIES_CANONICAL) {
+            if (p->k > 16384) return fail(KVC_ERR_UNSUPPORTED, "tie_mode canonical: k=%d > 16384 (the LDS sort of the selected set) not built", p->k);
+            if (n_sel > 131072) return fail(KVC_ERR_UNSUPPORTED, "tie_mode canonical: more than 131072 candidates per head not built (torch_cpu has no such limit)");
+        } else if ((int64_t)p->k * 64 <= n_sel && p->k > 18000) {
+            return fail(KVC_ERR_UNSUPPORTED, "tie_mode torch_cpu: a partial_sort heap of k=%d does not fit in LDS", p->k);
+        }
+        if (int rc = dc_strides("ring", es, p->ring_stride_b, p->ring_stride_h, p->window, p->n_q_heads, D)) return rc;
+    }
+    if (p->prefix_rows > 0)
+        if (int rc = dc_strides("prefix", es, p->prefix_stride_b, p->prefix_stride_h, p->prefix_rows, p->n_q_heads, D)) return rc;
+    if (int rc = dc_strides("tail", es, p->tail_stride_b, p->tail_stride_h, p->tail_rows, p->n_kv_heads, D)) return rc;
+    if (int rc = dc_strides("out", es, p->out_stride_b, p->out_stride_h, (int64_t)p->k + p->window, p->n_q_heads, D)) return rc;
+    return KVC_OK;
+}
+
+// kvc_params of the equivalent kvc_compress call, for the workspace layout and the selection.  n_kv_heads stays H_kv (the
+// materialised K would have H_q): carve() reads it only to pick its tile count, the scan takes at most that many partitions,
+// and the row-maxima region is sized by bsz * H_q * tile count either way.
+kvc_params dc_as_compress(const kvc_decode_compress_params* p) {
+    kvc_params c;
+    std::memset(&c, 0, sizeof(c));
+    c.method = p->method; c.dtype = p->dtype; c.bsz = p->bsz; c.n_q_heads = p->n_q_heads; c.n_kv_heads = p->n_kv_heads;
+    c.q_len = p->prefix_rows + p->tail_rows; c.head_dim = p->head_dim; c.window = p->window; c.k = p->k;
+    c.kernel_size = p->kernel_size; c.pooling = p->pooling; c.tie_mode = p->tie_mode; c.dot_mode = KVC_DOT_EXACT;
+    return c;
+}
+
+size_t dc_workspace(const kvc_params& c) {
+    if (!dc_scoring(c.method)) return 0;
+    return carve(&c).total + exact_scratch_total(&c, 1, &c.k);
+}
+
+struct Span { uintptr_t lo, hi; };
+Span dc_span(const void* ptr, int64_t sb, int64_t sh, int bsz, int heads, int64_t rows, int head_dim, int es) {
+    const uintptr_t lo = (uintptr_t)ptr;
+    return {lo, lo + (uintptr_t)(((int64_t)(bsz - 1) * sb + (int64_t)(heads - 1) * sh + rows * head_dim) * es)};
+}
+inline bool overlaps(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+}  // namespace
+
+extern "C" {
+
+__attribute__((visibility("default"))) size_t kvc_decode_compress_workspace_bytes(const kvc_decode_compress_params* p) {
+    if (dc_check(p) != KVC_OK) return 0;
+    g_err[0] = 0;
+    const kvc_params c = dc_as_compress(p);
+    return dc_workspace(c);
+}
+
+__attribute__((visibility("default"))) int kvc_decode_compress(const kvc_decode_compress_params* p, const void* q_ring, const void* k_prefix,
+                                                               const void* v_prefix, const void* k_tail, const void* v_tail, void* k_out,
+                                                               void* v_out, int64_t* idx_out, void* scores_out, void* workspace,
+                                                               size_t workspace_bytes, void* hip_stream) {
+    if (int rc = dc_check(p)) return rc;
+    const bool sc = dc_scoring(p->method);
+    const int es = esize_of(p->dtype), D = p->head_dim, P = p->prefix_rows, T = p->tail_rows, W = p->window;
+    const int L = P + T, G = p->n_q_heads / p->n_kv_heads;
+    if (!k_tail || !v_tail || !k_out || !v_out) return fail(KVC_ERR_INVALID, "k_tail, v_tail, k_out and v_out must be non-NULL");
+    if (P > 0 && (!k_prefix || !v_prefix)) return fail(KVC_ERR_INVALID, "k_prefix and v_prefix must be non-NULL when prefix_rows > 0");
+    if (sc && !q_ring) return fail(KVC_ERR_INVALID, "q_ring must be non-NULL for scoring methods");
+    if (((uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)k_out | (uintptr_t)v_out) % 16 ||
+        (P > 0 && ((uintptr_t)k_prefix | (uintptr_t)v_prefix) % 16) || (sc && ((uintptr_t)q_ring) % 16))
+        return fail(KVC_ERR_ALIGNMENT, "q_ring / k_prefix / v_prefix / k_tail / v_tail / k_out / v_out not 16-byte aligned");
+    if (!sc && idx_out && p->k > 0)
+        return fail(KVC_ERR_UNSUPPORTED, "StreamingLLM: idx_out must be NULL (indices are arange(k), pyramidkv_utils.py:607)");
+    if ((idx_out && ((uintptr_t)idx_out) % 16) || (sc && scores_out && ((uintptr_t)scores_out) % 16))
+        return fail(KVC_ERR_ALIGNMENT, "idx_out / scores_out not 16-byte aligned");
+    {   // the output never aliases the input (nor K' the V')
+        const Span ko = dc_span(k_out, p->out_stride_b, p->out_stride_h, p->bsz, p->n_q_heads, p->k + W, D, es);
+        const Span vo = dc_span(v_out, p->out_stride_b, p->out_stride_h, p->bsz, p->n_q_heads, p->k + W, D, es);
+        const Span kt = dc_span(k_tail, p->tail_stride_b, p->tail_stride_h, p->bsz, p->n_kv_heads, T, D, es);
+        const Span vt = dc_span(v_tail, p->tail_stride_b, p->tail_stride_h, p->bsz, p->n_kv_heads, T, D, es);
+        bool bad = overlaps(ko, vo) || overlaps(ko, kt) || overlaps(ko, vt) || overlaps(vo, kt) || overlaps(vo, vt);
+        if (P > 0) {
+            const Span kp = dc_span(k_prefix, p->prefix_stride_b, p->prefix_stride_h, p->bsz, p->n_q_heads, P, D, es);
+            const Span vp = dc_span(v_prefix, p->prefix_stride_b, p->prefix_stride_h, p->bsz, p->n_q_heads, P, D, es);
+            bad = bad || overlaps(ko, kp) || overlaps(ko, vp) || overlaps(vo, kp) || overlaps(vo, vp);
+        }
+        if (bad) return fail(KVC_ERR_INVALID, "k_out / v_out overlap each other, the prefix or the tail (alternate two prefix buffers)");
+    }
+    const kvc_params c = dc_as_compress(p);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    char* ws = static_cast<char*>(workspace);
+    int64_t* idx = nullptr;
+    if (sc) {
+        const Layout l = carve(&c);
+        const size_t need = dc_workspace(c);
+        if (!workspace) return fail(KVC_ERR_WORKSPACE, "workspace is NULL, need %zu bytes", need);
+        if (((uintptr_t)workspace) % 256) return fail(KVC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+        if (workspace_bytes < need) return fail(KVC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+        // stage 1: the two-segment window scan -> logits + partition maxima in kvc_compress's workspace layout
+        const int n_parts = l.n_tiles < (L + 255) / 256 ? l.n_tiles : (L + 255) / 256;   // <= the layout's tile count, >= 1
+        kvc::DcScanArgs s;
+        std::memset(&s, 0, sizeof(s));
+        s.ring = q_ring; s.kp = k_prefix; s.kt = k_tail;
+        s.ring_sb = p->ring_stride_b; s.ring_sh = p->ring_stride_h;
+        s.kp_sb = p->prefix_stride_b; s.kp_sh = p->prefix_stride_h; s.kt_sb = p->tail_stride_b; s.kt_sh = p->tail_stride_h;
+        s.logits = ws + l.logits; s.pmax = reinterpret_cast<float*>(ws + l.pmax);
+        s.n_q_heads = p->n_q_heads; s.group = G; s.prefix_rows = P; s.q_len = L; s.window = W; s.ring_start = p->ring_start;
+        s.n_parts = n_parts; s.keys_per_part = (L + n_parts - 1) / n_parts;
+        s.sqrt_d = (float)std::sqrt((double)D);                 // math.sqrt(head_dim) -> fp32 (pyramidkv_utils.py:317)
+        if (int rc = kvc::launch_dc_scan(s, p->dtype, D, p->bsz, st)) return fail(rc, "no decode scan kernel for dtype %d head_dim %d", p->dtype, D);
+        if (int rc = hip_ok("decode compress scan launch")) return rc;
+        // stage 2: kvc_compress's softmax / window sum / pooling over those logits (stage mask 6: the K-scan is not enqueued)
+        void* scores = scores_out ? scores_out : ws + l.scores;
+        kvc::ScoreArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.scores.p[0] = scores;
+        a.n_items = 1;
+        a.ws = ws; a.ws_item_stride = (int64_t)l.total;
+        a.off_logits = (int64_t)l.logits; a.off_pmax = (int64_t)l.pmax;
+        a.off_rowmax = (int64_t)l.rowmax; a.off_rowsum = (int64_t)l.rowsum;
+        a.off_part16 = l.has_part16 ? (int64_t)l.psum : -1;
+        a.bsz = p->bsz; a.n_q_heads = p->n_q_heads; a.n_kv_heads = p->n_kv_heads; a.group = G;
+        a.q_len = L; a.window = W; a.n_tiles = n_parts;
+        a.kernel_size = p->kernel_size; a.pooling = p->pooling;
+        a.stage_mask = 6;
+        a.sqrt_d = s.sqrt_d;
+        if (int rc = kvc::launch_scores(a, p->dtype, D, st)) return fail(rc, "no scoring kernel for dtype %d head_dim %d", p->dtype, D);
+        if (int rc = hip_ok("decode compress softmax launch")) return rc;
+        // stage 3: the selection (never the fused select + gather: it has one gather source)
+        idx = idx_out ? idx_out : reinterpret_cast<int64_t*>(ws + l.idx);
+        if (p->k > 0) {
+            Items it;
+            std::memset(&it, 0, sizeof(it));
+            it.n = 1; it.scores[0] = scores; it.idx[0] = idx; it.keep[0] = p->k; it.k_max = p->k;
+            if (int rc = enqueue_select(&c, it, false, ws + l.total, st)) return rc;
+        }
+    }
+    // stage 4: the two-source gather (StreamingLLM: this alone, identity indices)
+    kvc::DcGatherArgs g;
+    std::memset(&g, 0, sizeof(g));
+    g.src_p[0] = k_prefix; g.src_p[1] = v_prefix; g.src_t[0] = k_tail; g.src_t[1] = v_tail; g.out[0] = k_out; g.out[1] = v_out;
+    g.idx = sc ? idx : nullptr;
+    g.p_sb = p->prefix_stride_b; g.p_sh = p->prefix_stride_h; g.t_sb = p->tail_stride_b; g.t_sh = p->tail_stride_h;
+    g.o_sb = p->out_stride_b; g.o_sh = p->out_stride_h;
+    g.n_q_heads = p->n_q_heads; g.group = G; g.prefix_rows = P; g.q_len = L; g.window = W; g.k = p->k;
+    g.esize = es; g.row_bytes = D * es;
+    kvc::launch_dc_gather(g, p->bsz, st);
+    return hip_ok("decode compress gather launch");
+}
+
+}  // extern "C"

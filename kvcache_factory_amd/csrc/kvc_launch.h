@@ -200,6 +200,22 @@ struct OSegArgs {          // the key and value pools of one quantized segment, 
 };
 struct DecodeOArgs { OSegArgs pre, qt; };
 
+struct DcScanArgs {        // kvc_decode_compress.hip: window scan over prefix (per query head) + tail (per KV head)
+    const void* ring; const void* kp; const void* kt;  // q ring [b][Hq][W][D], prefix [b][Hq][P][D], tail [b][Hkv][T][D]
+    int64_t ring_sb, ring_sh, kp_sb, kp_sh, kt_sb, kt_sh;   // elements, rows dense
+    void* logits;          // [bsz*Hq][L][W] dtype (ScoreArgs layout)
+    float* pmax;           // [bsz*Hq][n_parts][W] fp32
+    int n_q_heads, group, prefix_rows, q_len, window, ring_start, n_parts, keys_per_part;
+    float sqrt_d;
+};
+
+struct DcGatherArgs {      // two-source gather: kept row idx < P from the prefix, else from tail head h / G
+    const void* src_p[2]; const void* src_t[2]; void* out[2];    // [0] keys, [1] values
+    const int64_t* idx;    // [bsz*Hq][k], or null (identity: StreamingLLM)
+    int64_t p_sb, p_sh, t_sb, t_sh, o_sb, o_sh;        // elements, rows dense
+    int n_q_heads, group, prefix_rows, q_len, window, k, row_bytes, esize;
+};
+
 // Raise a kernel's dynamic-LDS limit above 64 KB once per (kernel instantiation, device): `cache` is a function-local
 // static array owned by the caller.  Never called again on the launch path, so launches stay graph-capturable.
 struct LdsCache { size_t ok[16]; };
@@ -245,6 +261,8 @@ int launch_quantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, i
 int launch_dequantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st);
 int launch_decode_step_quant_outliers(DecodeQArgs a, const DecodeOArgs& o, int dtype, int head_dim, int nbits, const DecodeArgs& append,
                                       hipStream_t st);
+int launch_dc_scan(const DcScanArgs& a, int dtype, int head_dim, int bsz, hipStream_t st);
+int launch_dc_gather(const DcGatherArgs& a, int bsz, hipStream_t st);
 int decode_splits(int bsz, int n_q_heads, int new_rows, int rows);
 size_t decode_part_bytes(int bsz, int n_q_heads, int new_rows, int head_dim, int splits);
 int launch_sort_prefix(const RaggedSortArgs& a, int dtype, void* scratch, hipStream_t st);
