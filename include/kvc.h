@@ -234,6 +234,23 @@ int kvc_decode_step2(const kvc_decode_params* p, const kvc_decode_ext* ext /* nu
                      const void* k_pruned /* nullable */, const int16_t* chan /* nullable */, void* out,
                      void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
 
+/* kvc_decode_step_rows: kvc_decode_step2 with ext == NULL for a BATCH whose rows hold different numbers of prefix rows (left-padded
+ * prompts of unequal length, each compressed as the sequence it is alone).  Batch row b sees prefix rows [0, prefix_rows_b[b]) of
+ * every one of its heads and the tail as in kvc_decode_step; nothing at or behind row prefix_rows_b[b] of a prefix buffer is read.
+ *   - prefix_rows_b: device array of bsz int32, read by the kernels only (the host never looks at it; it may be the product of
+ *     earlier work on the stream).  p->prefix_rows is the number of rows the prefix buffers hold per head: every entry is clamped
+ *     to [0, p->prefix_rows] on the device, so no value of the array makes the call read outside the buffers.
+ *   - the tail is uniform: tail_rows and new_rows hold for every batch row, and the step's rows are appended as in kvc_decode_step.
+ *   - workspace: kvc_decode_rows_workspace_bytes(p) bytes, 16-byte aligned, sized from the bound; less (or NULL) only reduces the
+ *     number of splits.  Its contents before the call do not matter: a split that has no rows for a short batch row writes nothing
+ *     and is not read.
+ * Two kernels for the whole batch (attention, merge of the splits) and one for the append; every argument is checked before any
+ * pointer is used; enqueue-only: no allocation, no synchronisation. */
+size_t kvc_decode_rows_workspace_bytes(const kvc_decode_params* p);
+int kvc_decode_step_rows(const kvc_decode_params* p, const int32_t* prefix_rows_b /* device, [bsz] */,
+                         const void* q, const void* k_new, const void* v_new, const void* k_prefix, const void* v_prefix,
+                         void* k_tail, void* v_tail, void* out, void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
+
 /* ---- decode-stage compression: re-compress the SPLIT decode cache in place (the reference's README TODO "Support KV cache
  * compression at decoding stage") ---------------------------------------------------------------------------------------------
  * The cache of one layer is the prefix [b][H_q][P][D] (per query head) and the tail [b][H_kv][T][D] (per KV head, the decoded

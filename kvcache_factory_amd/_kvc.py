@@ -30,7 +30,8 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_cam_workspace_bytes", "kvc_cam_plan", "kvc_cam_merge", "kvc_quantize_rows", "kvc_dequantize_rows",
            "kvc_decode_quant_workspace_bytes", "kvc_decode_step_quant", "kvc_quantize_rows_outliers",
            "kvc_dequantize_rows_outliers", "kvc_decode_quant_outliers_workspace_bytes", "kvc_decode_step_quant_outliers",
-           "kvc_decode_compress_workspace_bytes", "kvc_decode_compress")
+           "kvc_decode_compress_workspace_bytes", "kvc_decode_compress", "kvc_decode_rows_workspace_bytes",
+           "kvc_decode_step_rows")
 
 
 class KvcError(RuntimeError):
@@ -147,6 +148,9 @@ def lib():
         L.kvc_ragged_workspace_bytes.restype = sz
         L.kvc_ragged_plan.argtypes = [pp, vp, vp, ctypes.c_float, ctypes.c_int, vp, vp, vp, vp, sz, vp]
         L.kvc_ragged_compact.argtypes = [pp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp, sz, vp]
+        L.kvc_decode_rows_workspace_bytes.argtypes = [ctypes.POINTER(DecodeParams)]
+        L.kvc_decode_rows_workspace_bytes.restype = sz
+        L.kvc_decode_step_rows.argtypes = [ctypes.POINTER(DecodeParams)] + [vp] * 10 + [sz, vp]
         L.kvc_ragged_decode_step.argtypes = [ctypes.POINTER(RaggedDecodeParams)] + [vp] * 9
         L.kvc_select_workspace_bytes.argtypes = [pp]
         L.kvc_select_workspace_bytes.restype = sz
@@ -413,6 +417,38 @@ def decode_step(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail
     _check(_call(dev, lib().kvc_decode_step2, ctypes.byref(p), ctypes.byref(x), _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(k_prefix),
                  _ptr(v_prefix), _ptr(k_tail), _ptr(v_tail), _ptr(k_pruned if pruned_rows else None), _ptr(chan if pruned_rows else None),
                  _ptr(out), _ptr(ws), nbytes, _stream(dev)))
+    return out
+
+
+def decode_step_rows(q, k_new, v_new, k_prefix, v_prefix, rows_b, rows_max, k_tail, v_tail, tail_rows, scaling):
+    """One decode step for a batch with per-row prefix lengths (kvc_decode_step_rows): decode_step, except that batch row b attends
+    to the first rows_b[b] rows per query head of k_prefix / v_prefix [b, H_q, >= rows_max, D].  rows_b: int32 [b] on the device,
+    never read by the host; rows_max: the bound the kernel clamps it to (what the buffers hold)."""
+    _require_gpu(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, rows_b)
+    dev = _one_device(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, rows_b)
+    q, k_new, v_new = _last_dim_contig(q), _last_dim_contig(k_new), _last_dim_contig(v_new)
+    if k_new.stride() != v_new.stride():        # K comes out of RoPE contiguous, V is the projection's transposed view
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    b, hq, t, D = q.shape
+    assert rows_b.dtype == torch.int32 and rows_b.shape == (b,) and rows_b.is_contiguous()
+    assert 0 <= rows_max <= k_prefix.shape[2] and v_prefix.shape[2] >= rows_max
+    assert k_tail.shape[2] >= tail_rows + t and k_new.shape == v_new.shape and k_new.shape[2] == t
+    assert k_tail.stride() == v_tail.stride() and k_prefix.stride() == v_prefix.stride()
+    for x in (k_prefix, v_prefix, k_tail, v_tail):
+        assert x.stride(3) == 1 and x.stride(2) == D, "cache rows must be dense"
+    out = torch.empty(b, t, hq, D, dtype=q.dtype, device=dev)
+    p = DecodeParams()
+    p.dtype, p.bsz, p.n_q_heads, p.n_kv_heads, p.head_dim = DTYPES[q.dtype], b, hq, k_new.shape[1], D
+    p.prefix_rows, p.tail_rows, p.new_rows, p.scaling = rows_max, tail_rows, t, scaling
+    p.q_stride_b, p.q_stride_h, p.q_stride_l = q.stride(0), q.stride(1), q.stride(2)
+    p.new_stride_b, p.new_stride_h, p.new_stride_l = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    p.prefix_stride_b, p.prefix_stride_h = k_prefix.stride(0), k_prefix.stride(1)
+    p.tail_stride_b, p.tail_stride_h = k_tail.stride(0), k_tail.stride(1)
+    p.out_stride_b, p.out_stride_h, p.out_stride_l = out.stride(0), out.stride(2), out.stride(1)
+    nbytes = lib().kvc_decode_rows_workspace_bytes(ctypes.byref(p))
+    ws = workspace(dev, nbytes) if nbytes else None
+    _check(_call(dev, lib().kvc_decode_step_rows, ctypes.byref(p), _ptr(rows_b), _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(k_prefix),
+                 _ptr(v_prefix), _ptr(k_tail), _ptr(v_tail), _ptr(out), _ptr(ws), nbytes, _stream(dev)))
     return out
 
 

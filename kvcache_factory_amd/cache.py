@@ -70,7 +70,17 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
     SPLIT (used by the fused decode step, `decode_attend`): the prefix `[bsz, H_q, k + W, D]` stays exactly
     where the compression kernels wrote it and the decoded tokens go to a TAIL `[bsz, H_kv, capacity, D]` — once per KV
     head, not H_q / H_kv times, with no repeat_kv and no copy of the prefix.  `keys` / `values` materialise the reference's
-    view on demand (tests, tools); asking for them through `update` converts the layer to EXPANDED for good."""
+    view on demand (tests, tools); asking for them through `update` converts the layer to EXPANDED for good.
+
+    PER-ROW LENGTHS (a left-padded batch of unequal prompts, pyramidkv_utils.prefill_rows): every prompt keeps what it keeps
+    alone, so batch row b uses only the first rows[b] of the `_stored` = max(rows) prefix rows.  `_rows` holds rows[] on the
+    DEVICE (int32 [bsz]; one of `_batch_tensors`, so beam reordering and the other batch operations carry it along without a
+    host read); the host knows only `_stored` and that the rows differ (`has_holes()`).  Decoded rows
+    are uniform — the batch decodes in lockstep — and follow row `_stored` (EXPANDED) or live in the tail (SPLIT): the columns
+    [rows[b], _stored) of row b are HOLES.  The fused step never reads them (kvc_decode_step_rows); the reference-shaped form
+    hides them with the layer's own additive mask (`decode_mask`), not with a slice of the mask transformers built for the
+    padded prompt.  `keys` / `values` are the padded view, `row_lengths()` says what is real.  When every row keeps the same
+    number of rows there are no holes and the layer is what it is for an unpadded batch."""
 
     RESERVE = 256                       # spare rows allocated with the compressed prompt / tail rows allocated at a time
 
@@ -82,18 +92,22 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         self._ktail = self._vtail = None    # SPLIT form: [bsz, H_kv, capacity, D]
         self._tail = 0
         self._split = False
+        self._rows = None               # int32 [bsz] on the device: prefix rows in use per batch row (None: _stored for all)
+        self._holes = False             # the rows of the batch keep different numbers of prefix rows
+        self._padded = False            # the prompt was a left-padded batch (prefill_rows): the layer masks its own decode steps
+        self._pmax = 0                  # prefix rows per head the buffers hold (= _stored until `update` appends behind them)
 
     # ---- the reference's view --------------------------------------------------------------------------------------
     # (`keys` / `values` are plain attributes of DynamicLayer; here they are computed from the buffers)
     keys = property(lambda self: self._view(self._kbuf, self._ktail), _placeholder_only("keys"))
     values = property(lambda self: self._view(self._vbuf, self._vtail), _placeholder_only("values"))
-    _batch_tensors = ("_kbuf", "_vbuf", "_ktail", "_vtail")
+    _batch_tensors = ("_kbuf", "_vbuf", "_ktail", "_vtail", "_rows")
 
     def reset(self):
         """Back to an empty layer (the next forward is a prefill): buffers, lengths and the split state go."""
-        self._kbuf = self._vbuf = self._ktail = self._vtail = None
-        self._stored = self._tail = self.true_length = 0
-        self._split = False
+        self._kbuf = self._vbuf = self._ktail = self._vtail = self._rows = None
+        self._stored = self._tail = self.true_length = self._pmax = 0
+        self._split = self._holes = self._padded = False
 
     def _view(self, buf, tail):
         if buf is None:
@@ -145,7 +159,64 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         else:
             self._place(k_compressed, v_compressed, self.RESERVE)
         self._split, self._tail, self._ktail, self._vtail = False, 0, None, None
+        self._rows, self._holes, self._padded, self._pmax = None, False, False, self._stored
         self.true_length = int(true_length)
+
+    # ---- prefill of a left-padded batch: per-row lengths -----------------------------------------------------------------------
+    def reserve_rows(self, bsz, n_heads, rows, head_dim, dtype, device, spare):
+        """Buffers [bsz, H_q, max(rows) + spare, D] for a batch whose row b keeps rows[b] rows (host ints).  Layer types that
+        cannot hold unequal rows refuse HERE, before anything is allocated or written."""
+        return self.reserve(bsz, n_heads, max(rows) + spare, head_dim, dtype, device)
+
+    def prefill_rows(self, rows, true_length):
+        """Records what reserve_rows' buffers hold once the per-row compressions have run: row b its first rows[b] rows."""
+        n = max(rows)
+        self.prefill(self._kbuf[:, :, :n], self._vbuf[:, :, :n], true_length)
+        self._padded = True
+        if min(rows) != n:
+            self._holes = True
+            for b, r in enumerate(rows):                                # the holes are masked, but a masked NaN still poisons
+                if r < n:                                               # 0 * V in the reference-shaped form: they hold zeros
+                    self._kbuf[b, :, r:n].zero_()
+                    self._vbuf[b, :, r:n].zero_()
+            dev = self._kbuf.device
+            host = torch.tensor(rows, dtype=torch.int32)
+            # (a pinned source and a non-blocking copy: the prefill's only host wait is the read of the mask)
+            self._rows = host.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else host
+
+    def row_lengths(self):
+        """int32 [bsz] on the layer's device: the prefix rows batch row b really holds (`keys` / `values` are padded to the
+        longest).  No host read."""
+        if self._kbuf is None:
+            return None
+        if self._rows is None:
+            n = self._stored if self._split else self._pmax              # (EXPANDED: decoded rows follow the prefix in _kbuf)
+            return torch.full((self._kbuf.shape[0],), n, dtype=torch.int32, device=self._kbuf.device)
+        return self._rows
+
+    def has_holes(self):
+        return self._holes
+
+    def owns_mask(self):
+        """The prompt was a left-padded batch: a reference-shaped decode step takes `decode_mask`, not transformers' mask (built
+        for the padded prompt's columns, which are not the rows that were kept)."""
+        return self._padded
+
+    def decode_mask(self, query_length, dtype, total=None, bsz=None):
+        """The additive mask [bsz, 1, t, total] of a reference-shaped decode step over this layer AFTER `update` has appended
+        the step's t rows (total: the keys `update` returned, by default this layer's own rows): 0 = attend, finfo.min on the
+        hole columns [rows[b], first decoded row) of row b and on the step's own later tokens.  Every other stored row belongs
+        to the prompt it is stored for.  Built on the device (from `_rows` when the rows differ)."""
+        t = query_length
+        total = self._stored if total is None else total
+        dev = self._kbuf.device if self._kbuf is not None else self.device
+        bsz = self._kbuf.shape[0] if bsz is None else bsz
+        col = torch.arange(total, device=dev)
+        hidden = (col[None, :] > (total - t + torch.arange(t, device=dev))[:, None])[None, None]          # [1, 1, t, total]
+        if self._holes:
+            hole = (col[None, :] >= self._rows[:, None].to(col.dtype)) & (col[None, :] < self._pmax)      # [b, total]
+            hidden = hidden | hole[:, None, None, :]
+        return torch.zeros(bsz, 1, t, total, dtype=dtype, device=dev).masked_fill(hidden, torch.finfo(dtype).min)
 
     # ---- decode: the reference-shaped path ----------------------------------------------------------------------------
     def _expand(self):
@@ -191,11 +262,19 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
             kt[:, :, :self._tail].copy_(self._ktail[:, :, :self._tail])
             vt[:, :, :self._tail].copy_(self._vtail[:, :, :self._tail])
             self._ktail, self._vtail = kt, vt
-        out = _kvc.decode_step(query_states, key_states, value_states, self._kbuf, self._vbuf, self._stored,
-                               self._ktail, self._vtail, self._tail, scaling)
+        if b > 1 and type(self)._batched_step:                    # a batch: per-row prefix lengths, one launch for all rows
+            if self._rows is None or self._rows.shape[0] != b:
+                self._rows = self.row_lengths()
+            out = _kvc.decode_step_rows(query_states, key_states, value_states, self._kbuf, self._vbuf, self._rows, self._stored,
+                                        self._ktail, self._vtail, self._tail, scaling)
+        else:
+            out = _kvc.decode_step(query_states, key_states, value_states, self._kbuf, self._vbuf, self._stored,
+                                   self._ktail, self._vtail, self._tail, scaling)
         self._tail += t
         self.true_length += t
         return out
+
+    _batched_step = True                # bsz > 1 decode_attend calls go through kvc_decode_step_rows
 
     def can_split(self):
         """The fused decode step needs the prefix in this layer's own buffers (a layer that went through prefill)."""
@@ -216,6 +295,16 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
 
     def after_decode(self, cluster, query_states):
         """Called by the patched forwards after a decode step's attention; nothing to do unless the layer compresses at decode."""
+
+
+def _uniform_rows_only(self, bsz, n_heads, rows, head_dim, dtype, device, spare):
+    """reserve_rows of the layer types that only ever see K' / V' of one length per batch (decode-stage compression, the
+    quantized caches): a padded batch whose prompts keep different numbers of rows is refused before anything is stored."""
+    if min(rows) != max(rows):
+        raise NotImplementedError(f"kvcache_factory_amd: {type(self).__name__} holds the same number of rows for every prompt of a batch; "
+                                  f"this left-padded batch keeps {list(rows)} rows per prompt (prompts shorter than max_capacity_prompt "
+                                  "are passed through, PyramidKV budgets follow the prompt length) — use the plain cache for it")
+    return CompressedDynamicLayer.reserve_rows(self, bsz, n_heads, rows, head_dim, dtype, device, spare)
 
 
 def _check_interval(interval):
@@ -259,6 +348,8 @@ class DecodeCompressedLayer(CompressedDynamicLayer):
         self.compressions = 0
 
     _batch_tensors = CompressedDynamicLayer._batch_tensors + ("_kalt", "_valt", "_qring")
+    _batched_step = False
+    reserve_rows = _uniform_rows_only
 
     def reset(self):
         super().reset()
@@ -362,7 +453,7 @@ class DecodeCompressedLayer(CompressedDynamicLayer):
         # prefill's (spare rows, or a view into a slab shared by a group of layers) is dropped here
         keep = self._fits(old_k, rows) and self._fits(old_v, rows)
         self._kalt, self._valt = (old_k, old_v) if keep else (None, None)
-        self._stored = self._p0 = B
+        self._stored = self._p0 = self._pmax = B
         self.compressions += 1
 
 
@@ -429,6 +520,8 @@ class QuantizedCompressedLayer(CompressedDynamicLayer):
         self._mode = None                                        # None, "fused" or "shaped"
 
     _batch_tensors = CompressedDynamicLayer._batch_tensors + ("_pkc", "_pvc", "_pkm", "_pvm", "_tkc", "_tvc", "_tkm", "_tvm", "_rk", "_rv")
+    _batched_step = False
+    reserve_rows = _uniform_rows_only
 
     def reset(self):
         super().reset()

@@ -500,8 +500,10 @@ int decode_check(const kvc_decode_params* p, const kvc_decode_ext* x) {
 }
 int decode_run(const kvc_decode_params* p, const kvc_decode_ext* x, const void* q, const void* k_new, const void* v_new,
                const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail, const void* k_pruned, const int16_t* chan,
-               void* out, void* workspace, size_t workspace_bytes, void* hip_stream) {
+               void* out, void* workspace, size_t workspace_bytes, void* hip_stream, const int32_t* rows_b = nullptr, bool per_row = false) {
     if (int rc = decode_check(p, x)) return rc;
+    if (per_row && !rows_b) return fail(KVC_ERR_INVALID, "prefix_rows_b is NULL");
+    if (per_row && ((uintptr_t)rows_b) % 4) return fail(KVC_ERR_ALIGNMENT, "prefix_rows_b is not 4-byte aligned");
     const int pruned = x ? x->pruned_rows : 0;
     if (!q || !k_new || !v_new || !k_tail || !v_tail || !out || (p->prefix_rows > 0 && !k_prefix) || (p->prefix_rows + pruned > 0 && !v_prefix))
         return fail(KVC_ERR_INVALID, "q, k_new, v_new, the tail, out (and the prefix when it has rows) must be non-NULL");
@@ -534,10 +536,17 @@ int decode_run(const kvc_decode_params* p, const kvc_decode_ext* x, const void* 
     a.splits = 1;
     if (workspace) {                                                  // as many splits as the workspace handed over can hold
         const int rows = pruned + p->prefix_rows + p->tail_rows + p->new_rows;
-        int s = kvc::decode_splits(p->bsz, p->n_q_heads, p->new_rows, rows);
+        int s = per_row ? kvc::decode_rows_splits(p->bsz, p->n_q_heads, p->new_rows, rows) : kvc::decode_splits(p->bsz, p->n_q_heads, p->new_rows, rows);
         while (s > 1 && kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, s) > workspace_bytes) --s;
         if (((uintptr_t)workspace) % 16) return fail(KVC_ERR_ALIGNMENT, "workspace is not 16-byte aligned");
         a.splits = s; a.part = static_cast<float*>(workspace);
+    }
+    if (per_row) {                                                    // kvc_decode_step_rows: p->prefix_rows is the bound of rows_b[]
+        kvc::DecodeRowsArgs ra;
+        ra.a = a; ra.rows_b = rows_b;
+        if (int rc = kvc::launch_decode_step_rows(ra, p->dtype, p->head_dim, static_cast<hipStream_t>(hip_stream)))
+            return fail(rc, "no per-row decode kernel for dtype %d head_dim %d", p->dtype, p->head_dim);
+        return hip_ok("per-row decode step launch");
     }
     if (int rc = kvc::launch_decode_step(a, p->dtype, p->head_dim, static_cast<hipStream_t>(hip_stream)))
         return fail(rc, "no decode kernel for dtype %d head_dim %d", p->dtype, p->head_dim);
@@ -562,6 +571,20 @@ __attribute__((visibility("default"))) int kvc_decode_step2(const kvc_decode_par
                                                             const void* k_pruned, const int16_t* chan, void* out, void* workspace,
                                                             size_t workspace_bytes, void* hip_stream) {
     return decode_run(p, ext, q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, k_pruned, chan, out, workspace, workspace_bytes, hip_stream);
+}
+
+__attribute__((visibility("default"))) size_t kvc_decode_rows_workspace_bytes(const kvc_decode_params* p) {
+    if (decode_check(p, nullptr)) return 0;
+    const int rows = p->prefix_rows + p->tail_rows + p->new_rows;
+    return kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, kvc::decode_rows_splits(p->bsz, p->n_q_heads, p->new_rows, rows));
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_rows(const kvc_decode_params* p, const int32_t* prefix_rows_b, const void* q,
+                                                                const void* k_new, const void* v_new, const void* k_prefix, const void* v_prefix,
+                                                                void* k_tail, void* v_tail, void* out, void* workspace, size_t workspace_bytes,
+                                                                void* hip_stream) {
+    return decode_run(p, nullptr, q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, nullptr, nullptr, out, workspace, workspace_bytes,
+                      hip_stream, prefix_rows_b, true);
 }
 
 // ---- quantized decode cache (kvc_quant.hip) -------------------------------------------------------------------------------

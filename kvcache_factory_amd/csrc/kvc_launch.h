@@ -164,6 +164,11 @@ struct DecodeArgs {        // one decode step over the compacted cache (kvc_deco
     float* part; int splits, rows_per_split;          // workspace: (m, l, acc[D]) per (b, h, token, split)
 };
 
+struct DecodeRowsArgs {    // kvc_decode_rows.hip: DecodeArgs (pruned_rows = 0) + the prefix rows each batch row may see
+    DecodeArgs a;                                     // a.prefix_rows: what the buffers hold (the clamp of every entry)
+    const int32_t* rows_b;                            // [bsz], device
+};
+
 struct QuantArgs {         // kvc_quant.hip: quantize / de-quantize rows [row0, row0 + rows) of one segment (include/kvc.h layout)
     const void* src; void* dst;                       // [b][h][row][D] elements (quantize reads src, de-quantize writes dst)
     uint8_t* codes; const uint8_t* codes_in; float* meta; const float* meta_in;
@@ -254,6 +259,8 @@ int launch_cam_merge(const CamArgs& a, int dtype, int head_dim, hipStream_t st);
 int launch_decode_step(DecodeArgs a, int dtype, int head_dim, hipStream_t st);
 int launch_decode_append(const DecodeArgs& a, hipStream_t st);                       // the step's rows -> tail (kvc_decode.hip)
 int launch_decode_combine(const DecodeArgs& a, int dtype, int head_dim, hipStream_t st);   // splits -> out (kvc_decode.hip)
+int launch_decode_step_rows(DecodeRowsArgs a, int dtype, int head_dim, hipStream_t st);     // kvc_decode_rows.hip
+int decode_rows_splits(int bsz, int n_q_heads, int new_rows, int rows);
 int launch_quantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_dequantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_decode_step_quant(DecodeQArgs a, int dtype, int head_dim, int nbits, const DecodeArgs& append, hipStream_t st);

@@ -33,6 +33,7 @@ BATCH_LAYERS = os.environ.get("KVC_BATCH_LAYERS", "1") == "1"   # patched forwar
 GROUP_LAYERS = int(os.environ.get("KVC_GROUP_LAYERS", "8"))      # ... of this many layers each (0: the whole prompt at once)
 DECODE_KERNEL = os.environ.get("KVC_DECODE_KERNEL", "1") == "1"  # decode steps by kvc_decode_step over the split cache (N1)
 OVERLAP = os.environ.get("KVC_OVERLAP", "1") == "1"              # grouped flushes run on a side stream beside the model's prefill
+BATCH_DECODE = os.environ.get("KVC_BATCH_DECODE", "1") == "1"    # bsz > 1 decode steps by kvc_decode_step_rows (0: reference-shaped)
 SPARE_ROWS = 256                                         # decode rows per head reserved behind the compressed prompt
 RAGGED_SLACK = 256                                       # AdaKV / HeadKV: spare rows behind every head of the flattened cache
 
@@ -53,6 +54,68 @@ def _run(method, key_states, query_states, value_states, window, n_keep, kernel_
     k_out, v_out = _kvc.compress(method, query_states, key_states, value_states, window, n_keep,
                                  kernel_size, pooling if method != _kvc.H2O else None, TIE_MODE)
     return k_out, v_out
+
+
+def row_starts(attention_mask, bsz, q_len):
+    """start[b] = number of pad columns in front of row b of a LEFT-padded batch, from the mask transformers hands the attention
+    modules at a prefill: 4-D [b, 1, q, kv] (the last query row is read: bool with True = attend under sdpa, additive with
+    0 = attend under eager) or the tokenizer's 2-D [b, kv] (non-zero = attend).  The visible columns of a row must be a non-empty
+    suffix; anything else (right padding, a hole, a row that sees nothing) raises ValueError.  The lengths are needed on the host
+    (budgets, pass-through, buffer sizes, grouping): this is the ONE device-to-host read a padded prompt costs."""
+    m = attention_mask
+    if m.dim() == 4:
+        m = m[:, 0, -1, :]
+    elif m.dim() != 2:
+        raise ValueError(f"kvcache_factory_amd: cannot read the batch geometry from an attention mask of shape {tuple(attention_mask.shape)}")
+    vis = m if m.dtype == torch.bool else ((m == 0) if (attention_mask.dim() == 4 and m.is_floating_point()) else (m != 0))
+    if vis.shape[-1] != q_len or vis.shape[0] not in (1, bsz):
+        raise ValueError(f"kvcache_factory_amd: the attention mask covers {tuple(vis.shape)} (rows, columns), the prompt batch is "
+                         f"({bsz}, {q_len})")
+    vis = vis.expand(bsz, q_len)
+    count = vis.sum(-1)
+    suffix = (vis[:, 1:] | ~vis[:, :-1]).all(-1)                          # once a column is visible, all behind it are
+    counts, ok = torch.stack([count, suffix.to(count.dtype)]).tolist()    # the one read
+    for b, (n, good) in enumerate(zip(counts, ok)):
+        if n == 0:
+            raise ValueError(f"kvcache_factory_amd: row {b} of the batch has no visible column in the attention mask")
+        if not good:
+            raise ValueError(f"kvcache_factory_amd: batches must be LEFT-padded (row {b}: the visible columns of the attention mask are "
+                             "not a suffix — right padding or a hole); set tokenizer.padding_side = 'left'")
+    return tuple(q_len - int(n) for n in counts)
+
+
+def prefill_rows(cluster, layer, key_states, query_states, value_states, starts, num_key_value_groups, pending=None):
+    """The prefill of one layer for a left-padded batch: row b is compressed as the sequence K[b, :, start[b]:] it is alone (its own
+    pass-through test, PyramidKV budget and tie regime), through the entry points a bsz = 1 prompt takes, and written into row b
+    of the layer's buffers — the rows of a batch may keep different numbers of rows (layer.reserve_rows / prefill_rows).
+    pending (a PrefillBatch): SnapKV / PyramidKV / StreamingLLM rows are parked there, one bsz = 1 item per row — rows of equal
+    length (of all the parked layers) share one kvc_compress_batch call; otherwise, and for H2O / L2Norm, cluster.update_kv runs
+    per row.  Methods that have no per-row form refuse."""
+    bsz, num_heads, q_len, head_dim = cluster._prefill_shapes(key_states, query_states)
+    if cluster._method == _kvc.CAM or cluster.merge is not None:
+        what = "CAM" if cluster._method == _kvc.CAM else f"{cluster._name} with merge={cluster.merge!r}"
+        raise NotImplementedError(f"kvcache_factory_amd: {what} has no per-row form for a padded batch of unequal prompts; "
+                                  "run these prompts one at a time")
+    lens = [q_len - s for s in starts]
+    kept = [cluster._kept_rows(n) for n in lens]                      # None: the row is passed through
+    rows = [n if k is None else k for n, k in zip(lens, kept)]
+    _say(f"{cluster._name} rows per prompt {rows}")
+    kb, vb = layer.reserve_rows(bsz, num_heads, rows, head_dim, key_states.dtype, key_states.device, SPARE_ROWS)
+    g = num_heads // key_states.shape[1]
+    park = pending is not None and cluster._method in (_kvc.SNAPKV, _kvc.PYRAMIDKV, _kvc.STREAMINGLLM)
+    for b, (s, n, k) in enumerate(zip(starts, lens, kept)):
+        kr, qr, vr = key_states[b:b + 1, :, s:], query_states[b:b + 1, :, s:], value_states[b:b + 1, :, s:]
+        if k is None:                                                  # cached repeat_kv-expanded, like the reference's pass-through
+            kb[b:b + 1, :, :n].copy_(kr.repeat_interleave(g, dim=1) if g > 1 else kr)
+            vb[b:b + 1, :, :n].copy_(vr.repeat_interleave(g, dim=1) if g > 1 else vr)
+        elif park:
+            pending.add_row(cluster, kr, qr, vr, (kb[b:b + 1], vb[b:b + 1]), tag=layer)
+        else:
+            kc, vc = cluster.update_kv(kr, qr, vr, None, num_key_value_groups)
+            kb[b:b + 1, :, :k].copy_(kc)
+            vb[b:b + 1, :, :k].copy_(vc)
+    layer.prefill_rows(rows, q_len)
+    return rows
 
 
 class _KVCluster:
@@ -77,6 +140,10 @@ class _KVCluster:
         return self.max_capacity_prompt - self.window_size                 # k of .topk(k) at :334
 
     _method = None
+
+    def _kept_rows(self, q_len):
+        """Rows per head update_kv leaves of a prompt of q_len tokens; None = passed through (:314)."""
+        return None if q_len < self.max_capacity_prompt else self._budget(q_len) + self.window_size
 
     def update_kv(self, key_states, query_states, value_states, attention_mask, num_key_value_groups):
         """(key_states', value_states') — `attention_mask` and `num_key_value_groups` are accepted and, as in the
@@ -122,6 +189,34 @@ class PrefillBatch:
         self.entries = []
         self._events = []               # (event recorded on the side stream, device, output tensors, input tensors kept alive)
         self._flushes = 0
+        self._starts = self._geometry_of = None     # the current prompt's row geometry (left-padded batches)
+
+    def geometry(self, attention_mask, bsz, q_len, fresh):
+        """start[b] of the prompt batch being prefilled (row_starts), or None when nothing is padded.  Derived when `fresh` (the
+        prompt's first layer) and kept for its other layers: one device-to-host read per prompt.  bsz = 1 and a missing mask
+        never look at anything."""
+        if bsz == 1 or not torch.is_tensor(attention_mask):
+            self._starts = self._geometry_of = None
+            return None
+        if fresh or self._geometry_of != (bsz, q_len):
+            starts = row_starts(attention_mask, bsz, q_len)
+            self._starts, self._geometry_of = (starts if any(starts) else None), (bsz, q_len)
+        return self._starts
+
+    def add_row(self, cluster, key_states, query_states, value_states, out, tag=None):
+        """`add` for ONE row of a left-padded batch: bsz = 1 views of the row's own tokens; K' / V' go into out = (k_buf, v_buf),
+        bsz = 1 views of the owner's buffers.  Rows of one length share a layout, whatever layer they belong to."""
+        _, num_heads, q_len, _ = cluster._prefill_shapes(key_states, query_states)
+        n_keep = cluster._budget(q_len)
+        scoring = cluster._method != _kvc.STREAMINGLLM
+        if scoring and cluster.pooling not in ("avgpool", "maxpool"):
+            raise ValueError('Pooling method not supported')            # pyramidkv_utils.py:333
+        W = cluster.window_size
+        qw = _kvc._last_dim_contig(query_states)[:, :, q_len - W:, :] if scoring else None
+        k, v = _kvc._last_dim_contig(key_states), _kvc._last_dim_contig(value_states)
+        layout = (cluster._method, tuple(k.shape), k.stride(), v.stride(), qw.stride() if scoring else None, k.dtype, k.device,
+                  num_heads, W, cluster.kernel_size if scoring else 0, cluster.pooling if scoring else None)
+        self.entries.append((tag, layout, k, qw, v, n_keep, lambda kc, vc: None, lambda *shape, out=out: out))
 
     def __len__(self):
         return len(self.entries)
@@ -320,6 +415,9 @@ class L2NormCluster:
     gather run in the HIP library (kvc_l2norm_compress)."""
     _name, _method = "L2Norm", _kvc.L2NORM
     merge = None
+
+    def _kept_rows(self, q_len):
+        return None if q_len < self.max_capacity_prompt or self.layer_idx in self.skip_layers else self.max_capacity_prompt
 
     def __init__(self, max_capacity_prompt: int = 256 + 64, layer_idx: int = 0, skip_layers=()):
         self.reset(max_capacity_prompt, layer_idx, skip_layers)
