@@ -284,6 +284,61 @@ int kvc_decode_compress(const kvc_decode_compress_params* p, const void* q_ring,
                         const void* k_tail, const void* v_tail, void* k_out, void* v_out, int64_t* idx_out /* nullable */,
                         void* scores_out /* nullable */, void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* ---- heavy hitters at decode time (H2O's own rule: evict by the attention every later query paid) ---------------------------------
+ * Every stored row of the SPLIT decode cache carries an fp32 SCORE per QUERY head: score_prefix [b][H_q][prefix capacity] for the
+ * prefix rows and score_tail [b][H_q][tail capacity] for the tail rows (a tail row's K / V are shared by the G query heads of its
+ * KV head, its score is not).
+ *
+ * kvc_decode_step_scored: kvc_decode_step2 with ext == NULL, and for every new token i of the step, in ascending i, and every row
+ * r visible to it (its own row included)
+ *     score[h][r] += p_i[h][r],      p_i[h] = the softmax the step's attention uses for token i and head h,
+ * in fp32: p = exp2(s - M) / Lsum with s the row's log2-domain logit (the fp32 fmaf chain of the attention kernel), M and Lsum the
+ * merged maximum and sum of the (head, token).  A row appended by this step starts from 0: what score_tail rows
+ * [tail_rows, tail_rows + new_rows) held before the call does not matter, nor do the contents of the workspace.  Nothing at or
+ * behind the visible rows is read or written (K, V, scores).  Every row's probability is owned by one thread: no atomics, the
+ * result does not depend on scheduling.  `out` has kvc_decode_step2's bytes (the split plan is that of a kvc_decode_step2 call
+ * with its full workspace).  Launches: append, attention, merge of the splits (more than one split only), scoring — one more than
+ * kvc_decode_step2.  Workspace: kvc_decode_scored_workspace_bytes(p) bytes, 16-byte aligned, REQUIRED (it holds the logits
+ * [b * H_q][new_rows][prefix_rows + tail_rows + new_rows] fp32 besides the splits' partial results).  Score strides in floats,
+ * score pointers 4-byte aligned.  Every argument is checked before any pointer is used; enqueue-only. */
+typedef struct kvc_decode_scored_params {
+    kvc_decode_params step;                                 /* as for kvc_decode_step2 */
+    int64_t score_prefix_stride_b, score_prefix_stride_h;   /* score_prefix [b][h_q][row], >= prefix_rows per head */
+    int64_t score_tail_stride_b, score_tail_stride_h;       /* score_tail [b][h_q][row], >= tail_rows + new_rows per head */
+} kvc_decode_scored_params;
+size_t kvc_decode_scored_workspace_bytes(const kvc_decode_scored_params* p);
+int kvc_decode_step_scored(const kvc_decode_scored_params* p, const void* q, const void* k_new, const void* v_new,
+                           const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail,
+                           float* score_prefix, float* score_tail, void* out,
+                           void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* kvc_decode_evict: the S = P + T rows of one layer become k + W rows.  With the virtual row numbering of kvc_decode_compress
+ * (row r < P: prefix row r of query head h; else tail row r - P of KV head h / G) and score[h][r] read from score_prefix /
+ * score_tail alike:
+ *     idx[h] = topk(score[h][0 : S - W], k).indices     tie_mode as kvc_select defines it for fp32 scores, no pooling
+ *     k_out[h] = cat(K[h][idx[h]], K[h][S - W : S]),  v_out alike,  score_out[h] = cat(score[h][idx[h]], score[h][S - W : S])
+ * — every kept row keeps its score.  Stages: the candidates' scores laid out as one fp32 row per head, kvc_select's kernels, one
+ * gather launch for K, V and the scores.  k_out / v_out [b][H_q][k + W][D], score_out [b][H_q][k + W] fp32, idx_out (nullable)
+ * [b][H_q][k] int64.  Limits: head_dim 64 / 128, T >= W >= 1, 0 <= k <= S - W, kvc_select's tie-mode limits; every K / V pointer
+ * and stride 16-byte aligned, score pointers 4-byte aligned; k_out / v_out disjoint from each other, the prefix and the tail,
+ * score_out from score_prefix and score_tail (the output never aliases the input: a caller alternates two prefix buffers, each
+ * with its score buffer).  Workspace: kvc_decode_evict_workspace_bytes(p) bytes, 256-byte aligned.  Enqueue-only. */
+typedef struct kvc_decode_evict_params {
+    int32_t dtype, bsz, n_q_heads, n_kv_heads, head_dim;
+    int32_t prefix_rows, tail_rows; /* P (per query head), T >= window (per KV head); S = P + T */
+    int32_t window, k, tie_mode;
+    int64_t prefix_stride_b, prefix_stride_h;               /* k_prefix / v_prefix [b][h_q][row][D] */
+    int64_t tail_stride_b, tail_stride_h;                   /* k_tail / v_tail [b][h_kv][row][D] */
+    int64_t out_stride_b, out_stride_h;                     /* k_out / v_out [b][h_q][row][D] */
+    int64_t score_prefix_stride_b, score_prefix_stride_h;   /* floats */
+    int64_t score_tail_stride_b, score_tail_stride_h;
+    int64_t score_out_stride_b, score_out_stride_h;
+} kvc_decode_evict_params;
+size_t kvc_decode_evict_workspace_bytes(const kvc_decode_evict_params* p);
+int kvc_decode_evict(const kvc_decode_evict_params* p, const void* k_prefix, const void* v_prefix, const void* k_tail,
+                     const void* v_tail, const float* score_prefix, const float* score_tail, void* k_out, void* v_out,
+                     float* score_out, int64_t* idx_out /* nullable */, void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- quantized decode cache (KIVI-style, --quant_method kivi --nbits N of the reference's run scripts) ----------------------
  * Rule: asymmetric round-to-nearest, every group on its own in fp32 with the inputs widened exactly.  KEYS are grouped per
  * channel (G = group_size consecutive stored rows share one (scale, zero) per channel; a segment whose rows are not a multiple

@@ -10,11 +10,12 @@ there is no CPU or eager-PyTorch fallback: if the extension is missing the impor
 """
 __version__ = "0.1.0"
 __all__ = ["QuantizedCompressedCache", "QuantizedCompressedLayer", "KVQuantCompressedCache", "KVQuantCompressedLayer",
-           "DecodeCompressedCache", "DecodeCompressedLayer"]
+           "DecodeCompressedCache", "DecodeCompressedLayer", "HeavyHitterCache", "HeavyHitterLayer"]
 
 
 def __getattr__(name):
-    # the quantized and decode-compressed caches (cache.py) are exported lazily: importing the package does not import transformers
+    # the quantized, decode-compressed and heavy-hitter caches (cache.py) are exported lazily: importing the package does not
+    # import transformers
     if name in __all__:
         from . import cache
         return getattr(cache, name)

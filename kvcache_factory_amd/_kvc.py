@@ -31,7 +31,8 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_decode_quant_workspace_bytes", "kvc_decode_step_quant", "kvc_quantize_rows_outliers",
            "kvc_dequantize_rows_outliers", "kvc_decode_quant_outliers_workspace_bytes", "kvc_decode_step_quant_outliers",
            "kvc_decode_compress_workspace_bytes", "kvc_decode_compress", "kvc_decode_rows_workspace_bytes",
-           "kvc_decode_step_rows")
+           "kvc_decode_step_rows", "kvc_decode_scored_workspace_bytes", "kvc_decode_step_scored",
+           "kvc_decode_evict_workspace_bytes", "kvc_decode_evict")
 
 
 class KvcError(RuntimeError):
@@ -109,6 +110,19 @@ class DecodeCompressParams(ctypes.Structure):
                                       "tail_stride_h", "out_stride_b", "out_stride_h")]
 
 
+class DecodeScoredParams(ctypes.Structure):
+    _fields_ = [("step", DecodeParams)] + [(n, ctypes.c_int64) for n in (
+        "score_prefix_stride_b", "score_prefix_stride_h", "score_tail_stride_b", "score_tail_stride_h")]
+
+
+class DecodeEvictParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("dtype", "bsz", "n_q_heads", "n_kv_heads", "head_dim", "prefix_rows", "tail_rows",
+                                               "window", "k", "tie_mode")] + [
+        (n, ctypes.c_int64) for n in ("prefix_stride_b", "prefix_stride_h", "tail_stride_b", "tail_stride_h", "out_stride_b",
+                                      "out_stride_h", "score_prefix_stride_b", "score_prefix_stride_h", "score_tail_stride_b",
+                                      "score_tail_stride_h", "score_out_stride_b", "score_out_stride_h")]
+
+
 _lib = None
 
 
@@ -177,6 +191,13 @@ def lib():
         L.kvc_decode_compress_workspace_bytes.argtypes = [dc]
         L.kvc_decode_compress_workspace_bytes.restype = sz
         L.kvc_decode_compress.argtypes = [dc] + [vp] * 10 + [sz, vp]
+        ds, de = ctypes.POINTER(DecodeScoredParams), ctypes.POINTER(DecodeEvictParams)
+        L.kvc_decode_scored_workspace_bytes.argtypes = [ds]
+        L.kvc_decode_scored_workspace_bytes.restype = sz
+        L.kvc_decode_step_scored.argtypes = [ds] + [vp] * 11 + [sz, vp]
+        L.kvc_decode_evict_workspace_bytes.argtypes = [de]
+        L.kvc_decode_evict_workspace_bytes.restype = sz
+        L.kvc_decode_evict.argtypes = [de] + [vp] * 11 + [sz, vp]
         _lib = L
     return _lib
 
@@ -511,6 +532,114 @@ def decode_compress(method, ring, ring_start, k_prefix, v_prefix, prefix_rows, k
         res.append(idx)
     if return_scores:
         res.append(sc)
+    return tuple(res)
+
+
+def decode_scored_params(q, k_new, k_prefix, prefix_rows, k_tail, tail_rows, score_prefix, score_tail, out, scaling):
+    """kvc_decode_scored_params of one call (tensors only describe shapes and strides; nothing is read).  out: [b, t, H_q, D]."""
+    sp = DecodeScoredParams()
+    p = sp.step
+    b, hq, t, D = q.shape
+    p.dtype, p.bsz, p.n_q_heads, p.n_kv_heads, p.head_dim = DTYPES[q.dtype], b, hq, k_new.shape[1], D
+    p.prefix_rows, p.tail_rows, p.new_rows, p.scaling = prefix_rows, tail_rows, t, scaling
+    p.q_stride_b, p.q_stride_h, p.q_stride_l = q.stride(0), q.stride(1), q.stride(2)
+    p.new_stride_b, p.new_stride_h, p.new_stride_l = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    if k_prefix is not None:
+        p.prefix_stride_b, p.prefix_stride_h = k_prefix.stride(0), k_prefix.stride(1)
+    p.tail_stride_b, p.tail_stride_h = k_tail.stride(0), k_tail.stride(1)
+    p.out_stride_b, p.out_stride_h, p.out_stride_l = out.stride(0), out.stride(2), out.stride(1)
+    if score_prefix is not None:
+        sp.score_prefix_stride_b, sp.score_prefix_stride_h = score_prefix.stride(0), score_prefix.stride(1)
+    sp.score_tail_stride_b, sp.score_tail_stride_h = score_tail.stride(0), score_tail.stride(1)
+    return sp
+
+
+def decode_step_scored(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_rows, score_prefix, score_tail, scaling,
+                       ws=None):
+    """decode_step (kvc_decode_step_scored) that also adds, for every new token in ascending order and every row visible to it,
+    the token's softmax probability to the row's fp32 score: score_prefix [b, H_q, >= prefix_rows] for the prefix rows,
+    score_tail [b, H_q, >= tail_rows + t] for the tail rows (one score per QUERY head; the step's own rows start from 0).
+    Returns the attention output [b, t, H_q, D], the bytes decode_step returns.  ws: a caller-owned workspace (uint8, at least
+    kvc_decode_scored_workspace_bytes) instead of the shared one."""
+    _require_gpu(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, score_prefix, score_tail)
+    dev = _one_device(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, score_prefix, score_tail)
+    q, k_new, v_new = _last_dim_contig(q), _last_dim_contig(k_new), _last_dim_contig(v_new)
+    if k_new.stride() != v_new.stride():        # K comes out of RoPE contiguous, V is the projection's transposed view
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    b, hq, t, D = q.shape
+    assert k_tail.shape[2] >= tail_rows + t and k_new.shape == v_new.shape and k_new.shape[2] == t
+    assert k_tail.stride() == v_tail.stride()
+    for x in (k_prefix, v_prefix, k_tail, v_tail):
+        if x is not None:
+            assert x.stride(3) == 1 and x.stride(2) == D, "cache rows must be dense"
+    if prefix_rows:
+        assert k_prefix.stride() == v_prefix.stride() and k_prefix.shape[2] >= prefix_rows
+        assert score_prefix.dtype == torch.float32 and score_prefix.shape[:2] == (b, hq) and score_prefix.shape[2] >= prefix_rows and \
+            score_prefix.stride(2) == 1
+    assert score_tail.dtype == torch.float32 and score_tail.shape[:2] == (b, hq) and score_tail.shape[2] >= tail_rows + t and \
+        score_tail.stride(2) == 1
+    out = torch.empty(b, t, hq, D, dtype=q.dtype, device=dev)
+    sp = decode_scored_params(q, k_new, k_prefix if prefix_rows else None, prefix_rows, k_tail, tail_rows,
+                              score_prefix if prefix_rows else None, score_tail, out, scaling)
+    nbytes = lib().kvc_decode_scored_workspace_bytes(ctypes.byref(sp))       # 0 for invalid params: the call below names the error
+    if ws is None:
+        ws = workspace(dev, nbytes) if nbytes else None
+    _check(_call(dev, lib().kvc_decode_step_scored, ctypes.byref(sp), _ptr(q), _ptr(k_new), _ptr(v_new),
+                 _ptr(k_prefix if prefix_rows else None), _ptr(v_prefix if prefix_rows else None), _ptr(k_tail), _ptr(v_tail),
+                 _ptr(score_prefix if prefix_rows else None), _ptr(score_tail), _ptr(out), _ptr(ws), nbytes, _stream(dev)))
+    return out
+
+
+def decode_evict_params(k_prefix, prefix_rows, k_tail, tail_rows, score_prefix, score_tail, out, score_out, window, n_keep,
+                        tie_mode="torch_cpu"):
+    """kvc_decode_evict_params of one call (tensors only describe shapes and strides; nothing is read)."""
+    p = DecodeEvictParams()
+    b, hkv, _, D = k_tail.shape
+    p.dtype, p.bsz, p.n_q_heads, p.n_kv_heads, p.head_dim = DTYPES[k_tail.dtype], b, out.shape[1], hkv, D
+    p.prefix_rows, p.tail_rows, p.window, p.k = prefix_rows, tail_rows, window, n_keep
+    p.tie_mode = TIE_MODES[tie_mode] if isinstance(tie_mode, str) else tie_mode
+    if k_prefix is not None:
+        p.prefix_stride_b, p.prefix_stride_h = k_prefix.stride(0), k_prefix.stride(1)
+        p.score_prefix_stride_b, p.score_prefix_stride_h = score_prefix.stride(0), score_prefix.stride(1)
+    p.tail_stride_b, p.tail_stride_h = k_tail.stride(0), k_tail.stride(1)
+    p.out_stride_b, p.out_stride_h = out.stride(0), out.stride(1)
+    p.score_tail_stride_b, p.score_tail_stride_h = score_tail.stride(0), score_tail.stride(1)
+    p.score_out_stride_b, p.score_out_stride_h = score_out.stride(0), score_out.stride(1)
+    return p
+
+
+def decode_evict(k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_rows, score_prefix, score_tail, out, score_out, window, n_keep,
+                 tie_mode="torch_cpu", return_indices=False):
+    """kvc_decode_evict: H2O's eviction on the SPLIT decode cache of one layer.  Of the S = prefix_rows + tail_rows rows of every
+    query head the n_keep with the largest fp32 scores among the first S - window (kvc_select's order and tie rule) and the last
+    `window` rows are written — K, V and their scores — into out = (k_buf, v_buf) [b, H_q, >= n_keep + window, D] and score_out
+    [b, H_q, >= n_keep + window] fp32, all disjoint from the inputs.  Returns views (k_out, v_out, score_out[, idx])."""
+    _require_gpu(k_prefix, v_prefix, k_tail, v_tail, score_prefix, score_tail, score_out, *out)
+    dev = _one_device(k_prefix, v_prefix, k_tail, v_tail, score_prefix, score_tail, score_out, *out)
+    kb, vb = out
+    assert kb.shape == vb.shape and kb.stride() == vb.stride() and k_tail.stride() == v_tail.stride()
+    if prefix_rows:
+        assert k_prefix.stride() == v_prefix.stride()
+    for t in (k_prefix if prefix_rows else None, k_tail, kb):
+        if t is not None:
+            assert t.stride(3) == 1 and t.stride(2) == t.shape[3], "rows must be dense"
+    for t in (score_prefix if prefix_rows else None, score_tail, score_out):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.dim() == 3 and t.stride(2) == 1
+    p = decode_evict_params(k_prefix if prefix_rows else None, prefix_rows, k_tail, tail_rows, score_prefix, score_tail, kb, score_out,
+                            window, n_keep, tie_mode)
+    b, hq = kb.shape[0], kb.shape[1]
+    idx = torch.empty(b, hq, n_keep, dtype=torch.int64, device=dev) if return_indices else None
+    L_ = lib()
+    nbytes = L_.kvc_decode_evict_workspace_bytes(ctypes.byref(p))       # 0 for invalid params: the call below names the error
+    ws = workspace(dev, nbytes) if nbytes else None
+    _check(_call(dev, L_.kvc_decode_evict, ctypes.byref(p), _ptr(k_prefix if prefix_rows else None), _ptr(v_prefix if prefix_rows else None),
+                 _ptr(k_tail), _ptr(v_tail), _ptr(score_prefix if prefix_rows else None), _ptr(score_tail), _ptr(kb), _ptr(vb),
+                 _ptr(score_out), _ptr(idx), _ptr(ws), nbytes, _stream(dev)))
+    rows = n_keep + window
+    res = [kb[:, :, :rows], vb[:, :, :rows], score_out[:, :, :rows]]
+    if return_indices:
+        res.append(idx)
     return tuple(res)
 
 

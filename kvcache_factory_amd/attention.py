@@ -25,8 +25,8 @@ import torch
 from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
 
 from . import pyramidkv_utils as pu
-from .cache import DECODE_METHODS, CompressedDynamicLayer, DecodeCompressedCache, QuantizedCompressedCache, RaggedDynamicLayer, \
-    ThinkDynamicLayer
+from .cache import DECODE_METHODS, CompressedDynamicLayer, DecodeCompressedCache, HeavyHitterCache, QuantizedCompressedCache, \
+    RaggedDynamicLayer, ThinkDynamicLayer
 
 _INIT = {
     "pyramidkv": lambda self: pu.init_pyramidkv(self, num_hidden_layers=self.config.num_hidden_layers),
@@ -100,6 +100,21 @@ def _refuse_decode_compressed(cache, method, cluster=None):
                                   "here; DecodeCompressedCache needs merge=None")
 
 
+def _refuse_heavy_hitter(cache, method, cluster=None, bsz=1):
+    """HeavyHitterCache is H2O's decode-time rule: the h2o patch, no pivot merge, one sequence.  Raised before anything is stored."""
+    if not isinstance(cache, HeavyHitterCache):
+        return
+    if method != "h2o":
+        raise NotImplementedError(f"kvcache_factory_amd: HeavyHitterCache evicts by H2O's accumulated attention; {method} has no such "
+                                  "rule here — it is built for the h2o path only")
+    if cluster is not None and getattr(cluster, "merge", None) is not None:
+        raise NotImplementedError(f"kvcache_factory_amd: h2o with merge={cluster.merge!r} has no decode-time eviction rule here; "
+                                  "HeavyHitterCache needs merge=None")
+    if bsz != 1:
+        raise NotImplementedError(f"kvcache_factory_amd: HeavyHitterCache holds one sequence (bsz = 1), got a batch of {bsz} "
+                                  "(beam search and num_return_sequences > 1 make one too)")
+
+
 def _pending_for(cache):
     """The prompt's PrefillBatch, kept on the cache object (one per generation)."""
     pending = getattr(cache, "_kvc_pending", None)
@@ -114,6 +129,7 @@ def make_forward(method, apply_rotary_pos_emb, eager_attention_forward, repeat_k
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
         init(self)
         _refuse_decode_compressed(past_key_values, method, self.kv_cluster)
+        _refuse_heavy_hitter(past_key_values, method, self.kv_cluster, hidden_states.shape[0])
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)
         query_states = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)
@@ -141,7 +157,10 @@ def make_forward(method, apply_rotary_pos_emb, eager_attention_forward, repeat_k
                     key_states = repeat_kv(key_states, self.num_key_value_groups)
                     value_states = repeat_kv(value_states, self.num_key_value_groups).contiguous()
                     attn_module = _OneGroup(self)
-                taken = starts is not None or pu.BATCH_LAYERS and pending.add(
+                heavy = isinstance(past_key_values, HeavyHitterCache)
+                if heavy:                                                    # the H2O compression, its indices and column sums
+                    pu.prefill_heavy_hitter(self.kv_cluster, layer, key_states, query_states, value_states)   # kept by the layer
+                taken = heavy or starts is not None or pu.BATCH_LAYERS and pending.add(
                     self.kv_cluster, key_states, query_states, value_states,
                     lambda kc, vc, layer=layer, q_len=q_len: layer.prefill(kc, vc, q_len), tag=layer,
                     alloc=layer.reserve)                                     # K' / V' land in the decode cache itself
@@ -214,6 +233,7 @@ def make_ragged_forward(method, apply_rotary_pos_emb, eager_attention_forward, r
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
         _refuse_quantized(past_key_values, method)
         _refuse_decode_compressed(past_key_values, method)
+        _refuse_heavy_hitter(past_key_values, method)
         init(self)
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)
@@ -261,6 +281,7 @@ def make_think_forward(apply_rotary_pos_emb, eager_attention_forward, repeat_kv)
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
         _refuse_quantized(past_key_values, "think")
         _refuse_decode_compressed(past_key_values, "think")
+        _refuse_heavy_hitter(past_key_values, "think")
         pu.init_think(self)
         input_shape = hidden_states.shape[:-1]
         hidden_shape = (*input_shape, -1, self.head_dim)

@@ -474,6 +474,189 @@ class DecodeCompressedCache(Cache):
         super().__init__(layers=[DecodeCompressedLayer(interval) for _ in range(text.num_hidden_layers)])
 
 
+class HeavyHitterLayer(CompressedDynamicLayer):
+    """A CompressedDynamicLayer that keeps evicting while it decodes, by H2O's own rule: every stored row carries, per QUERY
+    head, the fp32 sum of the attention every later query paid to it, and the rows with the smallest sums go.
+
+    Scores.  Prefill: the prompt is compressed by the H2O path unchanged; kept row j < k starts at the prompt's column sum
+    kvc_compress returned for it (widened exactly), the W window rows and every row of a pass-through prompt at 0.  Every
+    decode step (kvc_decode_step_scored): for each new token in ascending order and each row visible to it, its own included,
+    score += the softmax probability the step's attention used; a row appended by the step starts from 0.
+
+    Eviction.  B = max_capacity_prompt, W = window_size.  After a step (attention and scoring included) the layer holds
+    S = P + T rows, P per query head (the prefix) and T decoded rows (the tail, K / V once per KV head, scores per query head).
+    When S >= B + interval and T >= W, kvc_decode_evict keeps k = B - W rows by topk(score[0 : S - W], k) under the current
+    TIE_MODE, in top-k order, then the last W rows — K, V and scores — in the other of two B-row prefix buffers (each with its
+    score buffer); the tail buffers are reused.  `true_length` keeps counting every token.  At most B + interval + t - 1 rows
+    are stored per layer, t the tokens of a step.
+
+    SPLIT form only: the scores are a by-product of the fused step, so a step that cannot take it (`update`: bsz > 1, beams,
+    output_attentions, DECODE_KERNEL = 0, a sliding window, CPU tensors) is refused instead of silently dropping them.
+    Nothing on the decode path copies from the device to the host: the trigger is host arithmetic on the lengths."""
+
+    def __init__(self, interval=128):
+        _check_interval(interval)
+        super().__init__()
+        self.interval = interval
+        self._clear_scores()
+
+    def _clear_scores(self):
+        self._sbuf = None                   # fp32 [b, H_q, rows of _kbuf]: scores of the prefix rows
+        self._stail = None                  # fp32 [b, H_q, rows of _ktail]: scores of the tail rows, one per QUERY head
+        self._kalt = self._valt = self._salt = None     # the other prefix buffers: evictions alternate between the two
+        self._plan = None                   # (B, W) of this prompt, set at its first decode step
+        self.evictions = 0
+
+    _batch_tensors = CompressedDynamicLayer._batch_tensors + ("_sbuf", "_stail", "_kalt", "_valt", "_salt")
+    _batched_step = False
+
+    def _one_sequence(self, *a, **kw):
+        raise NotImplementedError("kvcache_factory_amd: HeavyHitterCache holds one sequence (bsz = 1): beam search, "
+                                  "num_return_sequences > 1 and batches are not supported")
+    reserve_rows = reorder_cache = batch_repeat_interleave = batch_select_indices = _one_sequence
+
+    def reset(self):
+        super().reset()
+        self._clear_scores()
+
+    def prefill(self, k_compressed, v_compressed, true_length):
+        if k_compressed.shape[0] != 1:
+            self._one_sequence()
+        super().prefill(k_compressed, v_compressed, true_length)
+        self._clear_scores()
+        kb = self._kbuf
+        self._sbuf = torch.zeros(kb.shape[0], kb.shape[1], kb.shape[2], dtype=torch.float32, device=kb.device)
+
+    def prefill_scores(self, idx, scores):
+        """The H2O compression's own outputs: idx [b, H_q, k] int64 and the prompt's column sums scores [b, H_q, L - W] in the
+        cache dtype.  Kept row j starts at float(scores[h][idx[h][j]]); the window rows stay at 0."""
+        k = idx.shape[2]
+        assert k <= self._stored and idx.shape[:2] == self._sbuf.shape[:2]
+        self._sbuf[:, :, :k].copy_(scores.gather(2, idx).to(torch.float32))
+
+    def update(self, key_states, value_states, *args, **kwargs):
+        if self._kbuf is None:
+            raise NotImplementedError("kvcache_factory_amd: HeavyHitterCache needs a model patched with h2o (this layer never went "
+                                      "through a compressing prefill, e.g. fullkv)")
+        raise NotImplementedError("kvcache_factory_amd: HeavyHitterCache scores its rows inside the fused decode step; this step "
+                                  "cannot take it (bsz > 1 or beams, output_attentions, KVC_DECODE_KERNEL=0, a sliding window, "
+                                  "training mode or tensors that are not on the GPU) and is refused rather than left unscored")
+
+    def rows(self):
+        """(P, T): prefix rows per query head and decoded rows since the prefill or the last eviction."""
+        return self._stored, (self._tail if self._split else 0)
+
+    def scores(self):
+        """fp32 [b, H_q, P + T]: the score of every stored row, prefix then tail (a copy; tests and tools)."""
+        P, T = self.rows()
+        if self._sbuf is None:
+            return None
+        pre = self._sbuf[:, :, :P]
+        return pre.clone() if T == 0 else torch.cat([pre, self._stail[:, :, :T]], dim=2)
+
+    def budget(self, cluster):
+        """(B, W) of this layer for `cluster` (the patched forward's kv_cluster)."""
+        from . import _kvc
+        if getattr(cluster, "_method", None) != _kvc.H2O or getattr(cluster, "merge", None) is not None:
+            raise NotImplementedError(f"kvcache_factory_amd: HeavyHitterCache is H2O's decode-time rule; it has none for "
+                                      f"{type(cluster).__name__} (merge={getattr(cluster, 'merge', None)!r})")
+        W = cluster.window_size
+        if self.interval < W:
+            raise ValueError(f"HeavyHitterCache: interval {self.interval} must be >= window_size {W}")
+        return cluster.max_capacity_prompt, W
+
+    def decode_attend(self, query_states, key_states, value_states, scaling):
+        """One decode step in the SPLIT form (kvc_decode_step_scored): the step's rows [1, H_kv, t, D] go to the tail, every
+        visible row's score grows by the attention it received, and the attention output [1, t, H_q, D] comes back."""
+        from . import _kvc
+        b, hkv, t, d = key_states.shape
+        if b != 1:
+            self._one_sequence()
+        hq = self._kbuf.shape[1]
+        if not self._split:
+            self._split, self._tail = True, 0
+        if self._ktail is None:
+            self._ktail = torch.empty(b, hkv, max(self.RESERVE, t), d, dtype=key_states.dtype, device=key_states.device)
+            self._vtail = torch.empty_like(self._ktail)
+            self._stail = torch.empty(b, hq, self._ktail.shape[2], dtype=torch.float32, device=key_states.device)
+        if self._tail + t > self._ktail.shape[2]:                 # tail full: double it (K, V and scores)
+            cap, n = max(2 * self._ktail.shape[2], self._tail + t), self._tail
+            kt = torch.empty(b, hkv, cap, d, dtype=self._ktail.dtype, device=self._ktail.device)
+            vt = torch.empty_like(kt)
+            st = torch.empty(b, hq, cap, dtype=torch.float32, device=self._ktail.device)
+            kt[:, :, :n].copy_(self._ktail[:, :, :n])
+            vt[:, :, :n].copy_(self._vtail[:, :, :n])
+            st[:, :, :n].copy_(self._stail[:, :, :n])
+            self._ktail, self._vtail, self._stail = kt, vt, st
+        out = _kvc.decode_step_scored(query_states, key_states, value_states, self._kbuf, self._vbuf, self._stored,
+                                      self._ktail, self._vtail, self._tail, self._sbuf, self._stail, scaling)
+        self._tail += t
+        self.true_length += t
+        return out
+
+    def after_decode(self, cluster, query_states):
+        if self._plan is None:
+            self._plan = self.budget(cluster)
+        B, W = self._plan
+        P, T = self.rows()
+        if P + T >= B + self.interval and T >= W:
+            self._evict(B, W, P, T)
+
+    def _fits(self, t, shape, dtype):
+        """t is a whole allocation of exactly `shape`: it may serve as an alternate prefix (or score) buffer."""
+        return t is not None and tuple(t.shape) == shape and t.dtype == dtype and t.device == self._kbuf.device and \
+            t.untyped_storage().nbytes() == t.numel() * t.element_size()
+
+    def _alt(self, rows):
+        """The other prefix buffers and their score buffer: exactly `rows` rows per head."""
+        kb = self._kbuf
+        kshape, sshape = (kb.shape[0], kb.shape[1], rows, kb.shape[3]), (kb.shape[0], kb.shape[1], rows)
+        if not (self._fits(self._kalt, kshape, kb.dtype) and self._fits(self._valt, kshape, kb.dtype) and
+                self._fits(self._salt, sshape, torch.float32)):
+            self._kalt = self._valt = self._salt = None                   # (released before the new set is allocated)
+            self._kalt = torch.empty(kshape, dtype=kb.dtype, device=kb.device)
+            self._valt = torch.empty_like(self._kalt)
+            self._salt = torch.empty(sshape, dtype=torch.float32, device=kb.device)
+        return self._kalt, self._valt, self._salt
+
+    def _evict(self, B, W, P, T):
+        from . import _kvc
+        from . import pyramidkv_utils as pu
+        kout, vout, sout = self._alt(B)
+        _kvc.decode_evict(self._kbuf, self._vbuf, P, self._ktail, self._vtail, T, self._sbuf, self._stail, (kout, vout), sout,
+                          W, B - W, pu.TIE_MODE)
+        old = (self._kbuf, self._vbuf, self._sbuf)
+        self._kbuf, self._vbuf, self._sbuf = kout, vout, sout
+        # the buffers evicted from become the next alternates only if they have exactly B rows; a prefill's buffer with spare
+        # rows (a pass-through prompt) is dropped here
+        kshape = tuple(kout.shape)
+        keep = self._fits(old[0], kshape, kout.dtype) and self._fits(old[1], kshape, kout.dtype) and \
+            self._fits(old[2], kshape[:3], torch.float32)
+        self._kalt, self._valt, self._salt = old if keep else (None, None, None)
+        self._tail = 0
+        self._stored = self._pmax = B
+        self.evictions += 1
+
+
+class HeavyHitterCache(Cache):
+    """A transformers Cache of HeavyHitterLayer, one per hidden layer: H2O as its paper runs it — the prompt is compressed at
+    prefill by the h2o patch as usual, every decode step adds the attention each cached row received to the row's score inside
+    the fused step, and every `interval` decoded tokens each layer drops its lowest-scoring rows back to max_capacity_prompt, so
+    memory and per-step attention stay bounded during long generations.
+
+        monkeypatch.replace_llama("h2o")
+        model.generate(ids, past_key_values=HeavyHitterCache(model.config, interval=128))
+
+    Works with the h2o patch only, bsz = 1; other methods, merge="pivot", an unpatched model (fullkv), batches / beams and steps
+    the fused decode kernel cannot take refuse it with NotImplementedError.  interval must be >= the config's window_size."""
+
+    def __init__(self, config, interval=128):
+        _check_interval(interval)
+        text = config.get_text_config() if hasattr(config, "get_text_config") else config
+        self.interval = interval
+        super().__init__(layers=[HeavyHitterLayer(interval) for _ in range(text.num_hidden_layers)])
+
+
 def _check_quant_args(nbits, q_group_size, residual_length):
     if nbits not in (2, 4, 8):
         raise ValueError(f"nbits must be 2, 4 or 8, got {nbits}")

@@ -1518,3 +1518,217 @@ __attribute__((visibility("default"))) int kvc_decode_compress(const kvc_decode_
 }
 
 }  // extern "C"
+
+// ---- heavy hitters at decode time (kvc_decode_scored.hip) ---------------------------------------------------------------------
+namespace {
+
+int score_strides(const char* what, int64_t sb, int64_t sh, int64_t rows, int heads) {
+    if (sh < rows || sb < (int64_t)heads * sh)
+        return fail(KVC_ERR_INVALID, "%s strides (%lld, %lld) smaller than its [heads=%d][rows=%lld] extent", what, (long long)sb, (long long)sh,
+                    heads, (long long)rows);
+    return KVC_OK;
+}
+
+// Every field of the params, before any pointer is looked at.
+int scored_check(const kvc_decode_scored_params* sp) {
+    if (!sp) return fail(KVC_ERR_INVALID, "params is NULL");
+    const kvc_decode_params* p = &sp->step;
+    if (int rc = decode_check(p, nullptr)) return rc;
+    const int64_t rows = (int64_t)p->prefix_rows + p->tail_rows + p->new_rows;
+    if (rows > 0x7fffffffLL) return fail(KVC_ERR_INVALID, "prefix_rows + tail_rows + new_rows overflows int32");
+    const int es = esize_of(p->dtype);
+    const int64_t strides[] = {p->q_stride_b, p->q_stride_h, p->q_stride_l, p->new_stride_b, p->new_stride_h, p->new_stride_l,
+                               p->prefix_stride_b, p->prefix_stride_h, p->tail_stride_b, p->tail_stride_h};
+    for (int64_t sd : strides) if ((sd * es) % 16) return fail(KVC_ERR_ALIGNMENT, "a stride is not a multiple of 16 bytes");
+    if (p->prefix_rows > 0)
+        if (int rc = score_strides("score_prefix", sp->score_prefix_stride_b, sp->score_prefix_stride_h, p->prefix_rows, p->n_q_heads)) return rc;
+    if (int rc = score_strides("score_tail", sp->score_tail_stride_b, sp->score_tail_stride_h, (int64_t)p->tail_rows + p->new_rows, p->n_q_heads))
+        return rc;
+    return KVC_OK;
+}
+
+struct ScoredLayout { int splits; size_t part, logit, total; };
+ScoredLayout scored_layout(const kvc_decode_params* p) {
+    ScoredLayout l;
+    const int rows = p->prefix_rows + p->tail_rows + p->new_rows;
+    const size_t items = (size_t)p->bsz * p->n_q_heads * p->new_rows;
+    l.splits = kvc::decode_splits(p->bsz, p->n_q_heads, p->new_rows, rows);                 // kvc_decode_step2's plan
+    l.part = 0;
+    l.logit = align_up(items * (size_t)l.splits * (p->head_dim + 2) * sizeof(float), 16);   // (M, Lsum) even with one split
+    l.total = align_up(l.logit + items * (size_t)rows * sizeof(float), 16);
+    return l;
+}
+
+int evict_check(const kvc_decode_evict_params* p) {
+    if (!p) return fail(KVC_ERR_INVALID, "params is NULL");
+    if (p->dtype < KVC_BF16 || p->dtype > KVC_FP32) return fail(KVC_ERR_INVALID, "unknown dtype %d", p->dtype);
+    if (p->bsz < 1 || p->n_q_heads < 1 || p->n_kv_heads < 1) return fail(KVC_ERR_INVALID, "bsz / head counts must be positive");
+    if (p->n_q_heads % p->n_kv_heads) return fail(KVC_ERR_INVALID, "n_q_heads %d not a multiple of n_kv_heads %d", p->n_q_heads, p->n_kv_heads);
+    if (p->head_dim != 64 && p->head_dim != 128) return fail(KVC_ERR_UNSUPPORTED, "decode eviction is built for head_dim 64 and 128, got %d", p->head_dim);
+    if (p->window < 1) return fail(KVC_ERR_INVALID, "window must be >= 1");
+    if (p->prefix_rows < 0) return fail(KVC_ERR_INVALID, "prefix_rows %d must be >= 0", p->prefix_rows);
+    if (p->tail_rows < p->window) return fail(KVC_ERR_INVALID, "tail_rows %d < window %d: the window rows come from the tail", p->tail_rows, p->window);
+    const int64_t S = (int64_t)p->prefix_rows + p->tail_rows;
+    if (S > 0x7fffffffLL) return fail(KVC_ERR_INVALID, "prefix_rows + tail_rows overflows int32");
+    const int64_t n = S - p->window;
+    if (p->k < 0 || p->k > n) return fail(KVC_ERR_INVALID, "k=%d outside [0, rows-window=%lld]", p->k, (long long)n);
+    if (p->tie_mode != KVC_TIES_TORCH_CPU && p->tie_mode != KVC_TIES_CANONICAL) return fail(KVC_ERR_INVALID, "unknown tie_mode %d", p->tie_mode);
+    if (p->tie_mode == KVC_TIES_CANONICAL) {
+        if (p->k > 16384) return fail(KVC_ERR_UNSUPPORTED, "tie_mode canonical: k=%d > 16384 (the LDS sort of the selected set) not built", p->k);
+        if (n > 131072) return fail(KVC_ERR_UNSUPPORTED, "tie_mode canonical: more than 131072 candidates per head not built (torch_cpu has no such limit)");
+    } else if ((int64_t)p->k * 64 <= n && p->k > 18000) {
+        return fail(KVC_ERR_UNSUPPORTED, "tie_mode torch_cpu: a partial_sort heap of k=%d does not fit in LDS", p->k);
+    }
+    const int es = esize_of(p->dtype), D = p->head_dim;
+    if (p->prefix_rows > 0) {
+        if (int rc = dc_strides("prefix", es, p->prefix_stride_b, p->prefix_stride_h, p->prefix_rows, p->n_q_heads, D)) return rc;
+        if (int rc = score_strides("score_prefix", p->score_prefix_stride_b, p->score_prefix_stride_h, p->prefix_rows, p->n_q_heads)) return rc;
+    }
+    if (int rc = dc_strides("tail", es, p->tail_stride_b, p->tail_stride_h, p->tail_rows, p->n_kv_heads, D)) return rc;
+    if (int rc = dc_strides("out", es, p->out_stride_b, p->out_stride_h, (int64_t)p->k + p->window, p->n_q_heads, D)) return rc;
+    if (int rc = score_strides("score_tail", p->score_tail_stride_b, p->score_tail_stride_h, p->tail_rows, p->n_q_heads)) return rc;
+    if (int rc = score_strides("score_out", p->score_out_stride_b, p->score_out_stride_h, (int64_t)p->k + p->window, p->n_q_heads)) return rc;
+    return KVC_OK;
+}
+
+struct EvictLayout { size_t cand, idx, exact, total; };
+EvictLayout evict_layout(const kvc_decode_evict_params* p) {
+    EvictLayout l;
+    const size_t heads = (size_t)p->bsz * p->n_q_heads, n = (size_t)p->prefix_rows + p->tail_rows - p->window;
+    l.cand = 0;
+    l.idx = align_up(heads * n * sizeof(float), 256);
+    l.exact = align_up(l.idx + heads * (size_t)p->k * 8, 256);
+    const size_t ex = (p->tie_mode == KVC_TIES_TORCH_CPU && p->k > 0) ? kvc::select_exact_scratch_bytes((int)heads, (int)n, p->k) : 0;
+    l.total = l.exact + align_up(ex, 256);
+    return l;
+}
+
+Span score_span(const float* ptr, int64_t sb, int64_t sh, int bsz, int heads, int64_t rows) {
+    const uintptr_t lo = (uintptr_t)ptr;
+    return {lo, lo + (uintptr_t)(((int64_t)(bsz - 1) * sb + (int64_t)(heads - 1) * sh + rows) * 4)};
+}
+
+}  // namespace
+
+extern "C" {
+
+__attribute__((visibility("default"))) size_t kvc_decode_scored_workspace_bytes(const kvc_decode_scored_params* p) {
+    if (scored_check(p) != KVC_OK) return 0;
+    g_err[0] = 0;
+    return scored_layout(&p->step).total;
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_scored(const kvc_decode_scored_params* sp, const void* q, const void* k_new,
+                                                                  const void* v_new, const void* k_prefix, const void* v_prefix, void* k_tail,
+                                                                  void* v_tail, float* score_prefix, float* score_tail, void* out,
+                                                                  void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = scored_check(sp)) return rc;
+    const kvc_decode_params* p = &sp->step;
+    if (!q || !k_new || !v_new || !k_tail || !v_tail || !out || !score_tail || (p->prefix_rows > 0 && (!k_prefix || !v_prefix || !score_prefix)))
+        return fail(KVC_ERR_INVALID, "q, k_new, v_new, the tail, score_tail, out (and the prefix and score_prefix when it has rows) must be non-NULL");
+    const void* ptrs[] = {q, k_new, v_new, k_tail, v_tail, p->prefix_rows > 0 ? k_prefix : nullptr, p->prefix_rows > 0 ? v_prefix : nullptr};
+    for (const void* ptr : ptrs) if (((uintptr_t)ptr) % 16) return fail(KVC_ERR_ALIGNMENT, "a pointer is not 16-byte aligned");
+    if (((uintptr_t)score_tail) % 4 || (p->prefix_rows > 0 && ((uintptr_t)score_prefix) % 4))
+        return fail(KVC_ERR_ALIGNMENT, "score_prefix / score_tail not 4-byte aligned");
+    const ScoredLayout l = scored_layout(p);
+    if (!workspace) return fail(KVC_ERR_WORKSPACE, "workspace is NULL, need %zu bytes", l.total);
+    if (((uintptr_t)workspace) % 16) return fail(KVC_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    if (workspace_bytes < l.total) return fail(KVC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, l.total);
+    const int es = esize_of(p->dtype);
+    kvc::DecodeScoredArgs sa;
+    std::memset(&sa, 0, sizeof(sa));
+    kvc::DecodeArgs& a = sa.a;
+    a.q = q; a.k_new = k_new; a.v_new = v_new; a.k_prefix = k_prefix; a.v_prefix = v_prefix; a.k_tail = k_tail; a.v_tail = v_tail; a.out = out;
+    a.q_stride_b = p->q_stride_b; a.q_stride_h = p->q_stride_h; a.q_stride_l = p->q_stride_l;
+    a.new_stride_b = p->new_stride_b; a.new_stride_h = p->new_stride_h; a.new_stride_l = p->new_stride_l;
+    a.prefix_stride_b = p->prefix_stride_b; a.prefix_stride_h = p->prefix_stride_h;
+    a.vprefix_stride_b = p->prefix_stride_b; a.vprefix_stride_h = p->prefix_stride_h;
+    a.tail_stride_b = p->tail_stride_b; a.tail_stride_h = p->tail_stride_h;
+    a.out_stride_b = p->out_stride_b; a.out_stride_h = p->out_stride_h; a.out_stride_l = p->out_stride_l;
+    a.bsz = p->bsz; a.n_q_heads = p->n_q_heads; a.n_kv_heads = p->n_kv_heads; a.group = p->n_q_heads / p->n_kv_heads;
+    a.prefix_rows = p->prefix_rows; a.tail_rows = p->tail_rows; a.new_rows = p->new_rows;
+    a.esize = es; a.row_bytes = p->head_dim * es; a.scaling = p->scaling;
+    a.splits = l.splits;
+    a.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + l.part);
+    sa.logit = reinterpret_cast<float*>(static_cast<char*>(workspace) + l.logit);
+    sa.score_prefix = score_prefix; sa.score_tail = score_tail;
+    sa.sp_sb = sp->score_prefix_stride_b; sa.sp_sh = sp->score_prefix_stride_h;
+    sa.st_sb = sp->score_tail_stride_b; sa.st_sh = sp->score_tail_stride_h;
+    if (int rc = kvc::launch_decode_step_scored(sa, p->dtype, p->head_dim, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no scored decode kernel for dtype %d head_dim %d", p->dtype, p->head_dim);
+    return hip_ok("scored decode step launch");
+}
+
+__attribute__((visibility("default"))) size_t kvc_decode_evict_workspace_bytes(const kvc_decode_evict_params* p) {
+    if (evict_check(p) != KVC_OK) return 0;
+    g_err[0] = 0;
+    return evict_layout(p).total;
+}
+
+__attribute__((visibility("default"))) int kvc_decode_evict(const kvc_decode_evict_params* p, const void* k_prefix, const void* v_prefix,
+                                                            const void* k_tail, const void* v_tail, const float* score_prefix,
+                                                            const float* score_tail, void* k_out, void* v_out, float* score_out,
+                                                            int64_t* idx_out, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = evict_check(p)) return rc;
+    const int es = esize_of(p->dtype), D = p->head_dim, P = p->prefix_rows, T = p->tail_rows, W = p->window;
+    const int n = P + T - W, G = p->n_q_heads / p->n_kv_heads;
+    if (!k_tail || !v_tail || !score_tail || !k_out || !v_out || !score_out)
+        return fail(KVC_ERR_INVALID, "k_tail, v_tail, score_tail, k_out, v_out and score_out must be non-NULL");
+    if (P > 0 && (!k_prefix || !v_prefix || !score_prefix))
+        return fail(KVC_ERR_INVALID, "k_prefix, v_prefix and score_prefix must be non-NULL when prefix_rows > 0");
+    if (((uintptr_t)k_tail | (uintptr_t)v_tail | (uintptr_t)k_out | (uintptr_t)v_out) % 16 || (P > 0 && ((uintptr_t)k_prefix | (uintptr_t)v_prefix) % 16))
+        return fail(KVC_ERR_ALIGNMENT, "k_prefix / v_prefix / k_tail / v_tail / k_out / v_out not 16-byte aligned");
+    if (((uintptr_t)score_tail | (uintptr_t)score_out) % 4 || (P > 0 && ((uintptr_t)score_prefix) % 4))
+        return fail(KVC_ERR_ALIGNMENT, "score_prefix / score_tail / score_out not 4-byte aligned");
+    if (idx_out && ((uintptr_t)idx_out) % 16) return fail(KVC_ERR_ALIGNMENT, "idx_out not 16-byte aligned");
+    {   // the output never aliases the input
+        const Span ko = dc_span(k_out, p->out_stride_b, p->out_stride_h, p->bsz, p->n_q_heads, p->k + W, D, es);
+        const Span vo = dc_span(v_out, p->out_stride_b, p->out_stride_h, p->bsz, p->n_q_heads, p->k + W, D, es);
+        const Span kt = dc_span(k_tail, p->tail_stride_b, p->tail_stride_h, p->bsz, p->n_kv_heads, T, D, es);
+        const Span vt = dc_span(v_tail, p->tail_stride_b, p->tail_stride_h, p->bsz, p->n_kv_heads, T, D, es);
+        const Span so = score_span(score_out, p->score_out_stride_b, p->score_out_stride_h, p->bsz, p->n_q_heads, p->k + W);
+        const Span stl = score_span(score_tail, p->score_tail_stride_b, p->score_tail_stride_h, p->bsz, p->n_q_heads, T);
+        bool bad = overlaps(ko, vo) || overlaps(ko, kt) || overlaps(ko, vt) || overlaps(vo, kt) || overlaps(vo, vt) || overlaps(so, stl);
+        if (P > 0) {
+            const Span kp = dc_span(k_prefix, p->prefix_stride_b, p->prefix_stride_h, p->bsz, p->n_q_heads, P, D, es);
+            const Span vp = dc_span(v_prefix, p->prefix_stride_b, p->prefix_stride_h, p->bsz, p->n_q_heads, P, D, es);
+            const Span spr = score_span(score_prefix, p->score_prefix_stride_b, p->score_prefix_stride_h, p->bsz, p->n_q_heads, P);
+            bad = bad || overlaps(ko, kp) || overlaps(ko, vp) || overlaps(vo, kp) || overlaps(vo, vp) || overlaps(so, spr);
+        }
+        if (bad) return fail(KVC_ERR_INVALID, "k_out / v_out / score_out overlap each other's inputs (alternate two prefix buffers, each with its scores)");
+    }
+    const EvictLayout l = evict_layout(p);
+    if (!workspace) return fail(KVC_ERR_WORKSPACE, "workspace is NULL, need %zu bytes", l.total);
+    if (((uintptr_t)workspace) % 256) return fail(KVC_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (workspace_bytes < l.total) return fail(KVC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, l.total);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    char* ws = static_cast<char*>(workspace);
+    kvc::EvictArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.score_p = score_prefix; a.score_t = score_tail; a.cand = reinterpret_cast<float*>(ws + l.cand); a.score_out = score_out;
+    a.src_p[0] = k_prefix; a.src_p[1] = v_prefix; a.src_t[0] = k_tail; a.src_t[1] = v_tail; a.out[0] = k_out; a.out[1] = v_out;
+    a.idx = idx_out ? idx_out : reinterpret_cast<int64_t*>(ws + l.idx);
+    a.sp_sb = p->score_prefix_stride_b; a.sp_sh = p->score_prefix_stride_h; a.st_sb = p->score_tail_stride_b; a.st_sh = p->score_tail_stride_h;
+    a.so_sb = p->score_out_stride_b; a.so_sh = p->score_out_stride_h;
+    a.p_sb = p->prefix_stride_b; a.p_sh = p->prefix_stride_h; a.t_sb = p->tail_stride_b; a.t_sh = p->tail_stride_h;
+    a.o_sb = p->out_stride_b; a.o_sh = p->out_stride_h;
+    a.n_q_heads = p->n_q_heads; a.group = G; a.prefix_rows = P; a.n = n; a.window = W; a.k = p->k; a.esize = es; a.row_bytes = D * es;
+    if (p->k > 0) {
+        // stage 1: the candidates' scores as one fp32 row per head; stage 2: kvc_select's kernels on it
+        kvc::launch_evict_scores(a, p->bsz, st);
+        if (int rc = hip_ok("decode evict score layout launch")) return rc;
+        kvc_params c;
+        std::memset(&c, 0, sizeof(c));
+        c.method = KVC_H2O; c.dtype = KVC_FP32; c.bsz = p->bsz; c.n_q_heads = p->n_q_heads; c.n_kv_heads = p->n_kv_heads;
+        c.q_len = P + T; c.head_dim = D; c.window = W; c.k = p->k; c.tie_mode = p->tie_mode; c.dot_mode = KVC_DOT_EXACT;
+        Items it;
+        std::memset(&it, 0, sizeof(it));
+        it.n = 1; it.scores[0] = a.cand; it.idx[0] = const_cast<int64_t*>(a.idx); it.keep[0] = p->k; it.k_max = p->k;
+        if (int rc = enqueue_select(&c, it, false, ws + l.exact, st)) return rc;
+    }
+    // stage 3: K, V and the scores of the kept rows, each from the segment that holds it
+    kvc::launch_evict_gather(a, p->bsz, st);
+    return hip_ok("decode evict gather launch");
+}
+
+}  // extern "C"

@@ -221,6 +221,24 @@ struct DcGatherArgs {      // two-source gather: kept row idx < P from the prefi
     int n_q_heads, group, prefix_rows, q_len, window, k, row_bytes, esize;
 };
 
+struct DecodeScoredArgs {  // kvc_decode_scored.hip: DecodeArgs (pruned_rows = 0; a.part written with one split too) + the scores
+    DecodeArgs a;
+    float* logit;          // [bsz*Hq][new_rows][rows] fp32 workspace: the log2-domain logit of every visible row
+    float* score_prefix; float* score_tail;            // [b][Hq][capacity] fp32, running sums of attention per stored row
+    int64_t sp_sb, sp_sh, st_sb, st_sh;                // floats
+    int rows;              // prefix_rows + tail_rows + new_rows (launcher-set)
+};
+
+struct EvictArgs {         // kvc_decode_evict: candidate scores -> one row per head; gather of K, V and scores from two segments
+    const float* score_p; const float* score_t; float* cand;     // cand [bsz*Hq][n] fp32 workspace
+    float* score_out;      // [b][Hq][k + window] fp32
+    const void* src_p[2]; const void* src_t[2]; void* out[2];    // [0] keys, [1] values
+    const int64_t* idx;    // [bsz*Hq][k] virtual row numbers
+    int64_t sp_sb, sp_sh, st_sb, st_sh, so_sb, so_sh;            // floats
+    int64_t p_sb, p_sh, t_sb, t_sh, o_sb, o_sh;                  // elements, rows dense
+    int n_q_heads, group, prefix_rows, n, window, k, row_bytes, esize;    // n = P + T - window candidates
+};
+
 // Raise a kernel's dynamic-LDS limit above 64 KB once per (kernel instantiation, device): `cache` is a function-local
 // static array owned by the caller.  Never called again on the launch path, so launches stay graph-capturable.
 struct LdsCache { size_t ok[16]; };
@@ -268,6 +286,9 @@ int launch_quantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, i
 int launch_dequantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st);
 int launch_decode_step_quant_outliers(DecodeQArgs a, const DecodeOArgs& o, int dtype, int head_dim, int nbits, const DecodeArgs& append,
                                       hipStream_t st);
+int launch_decode_step_scored(DecodeScoredArgs a, int dtype, int head_dim, hipStream_t st);   // kvc_decode_scored.hip
+int launch_evict_scores(const EvictArgs& a, int bsz, hipStream_t st);
+int launch_evict_gather(const EvictArgs& a, int bsz, hipStream_t st);
 int launch_dc_scan(const DcScanArgs& a, int dtype, int head_dim, int bsz, hipStream_t st);
 int launch_dc_gather(const DcGatherArgs& a, int bsz, hipStream_t st);
 int decode_splits(int bsz, int n_q_heads, int new_rows, int rows);

@@ -118,6 +118,26 @@ def prefill_rows(cluster, layer, key_states, query_states, value_states, starts,
     return rows
 
 
+def prefill_heavy_hitter(cluster, layer, key_states, query_states, value_states):
+    """The prefill of one layer of a HeavyHitterCache: H2OKVCluster.update_kv unchanged — same entry point, same arguments, K' / V'
+    written into the layer's own buffers — except that the indices and the column sums kvc_compress computes anyway are handed
+    to the layer (HeavyHitterLayer.prefill_scores): they are where H2O's running scores start.  A prompt shorter than
+    max_capacity_prompt is cached whole (repeat_kv-expanded, like the reference's pass-through) with every score at 0."""
+    bsz, num_heads, q_len, head_dim = cluster._prefill_shapes(key_states, query_states)
+    n_keep, W = cluster._budget(q_len), cluster.window_size
+    _say(f"{cluster._name} max_capacity_prompt {cluster.max_capacity_prompt}")
+    if q_len < cluster.max_capacity_prompt:                               # :314 pass-through
+        g = num_heads // key_states.shape[1]
+        layer.prefill(key_states.repeat_interleave(g, dim=1) if g > 1 else key_states,
+                      value_states.repeat_interleave(g, dim=1) if g > 1 else value_states, q_len)
+        return
+    out = layer.reserve(bsz, num_heads, n_keep + W, head_dim, key_states.dtype, key_states.device)   # exactly B rows: an alternate later
+    kc, vc, idx, sc = _kvc.compress(_kvc.H2O, query_states, key_states, value_states, W, n_keep, cluster.kernel_size, None, TIE_MODE,
+                                    return_indices=True, return_scores=True, out=out)
+    layer.prefill(kc, vc, q_len)
+    layer.prefill_scores(idx, sc)
+
+
 class _KVCluster:
     """State every reference cluster carries (ctor/reset of pyramidkv_utils.py:174-195, :286-304, :516-531,
     :579-593): the knobs only — clusters are stateless between calls."""
