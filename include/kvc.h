@@ -251,6 +251,33 @@ int kvc_decode_step_rows(const kvc_decode_params* p, const int32_t* prefix_rows_
                          const void* q, const void* k_new, const void* v_new, const void* k_prefix, const void* v_prefix,
                          void* k_tail, void* v_tail, void* out, void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
 
+/* kvc_decode_step_dev: kvc_decode_step_rows (kvc_decode_step2 with ext == NULL when prefix_rows_b is NULL) with the TAIL LENGTH read
+ * on the device, so that the call can be captured in a HIP graph and replayed while the cache grows.  The tail buffers hold
+ * tail_capacity rows per KV head;
+ *     T = clamp(*tail_rows_dev, 0, tail_capacity - new_rows)
+ * is read by the kernels only, p->tail_rows is ignored.  The step's rows are appended at tail row T; token i of batch row b sees
+ * prefix rows [0, P_b) and tail rows [0, T + i + 1), P_b = prefix_rows_b[b] clamped to [0, p->prefix_rows], or p->prefix_rows.
+ *   - THE RULE: nothing the host passes depends on T.  The grid and the rows of a split come from the bound
+ *     p->prefix_rows + tail_capacity; a workgroup whose first row is at or past the visible rows returns before it loads anything
+ *     and writes nothing, and the merge of the splits reads only those that ran.  Two calls with the same arguments differ only in
+ *     what the device finds in the counter: a captured call replays correctly for every later length.
+ *   - the library only READS the counter; the caller advances it by new_rows, in stream order, after the call (inside a captured
+ *     region: a device-side add), and moves to larger tail buffers before T + new_rows would pass tail_capacity.
+ *   - the clamp: no counter value makes a kernel read or write outside rows [0, tail_capacity) of the tail buffers.  Tail rows at
+ *     or behind T + new_rows are neither read nor written.
+ *   - workspace: kvc_decode_dev_workspace_bytes(p, tail_capacity) bytes, 16-byte aligned, sized from the bound; less (or NULL)
+ *     only reduces the number of splits.  Its contents before the call do not matter.  A captured call must own its workspace
+ *     (and `out`) for as long as the graph lives.
+ * Every argument is checked before any pointer is used (tail_capacity < new_rows and a NULL counter are KVC_ERR_INVALID);
+ * enqueue-only: no allocation, no synchronisation, no host read, no kernel attribute set on the launch path. */
+size_t kvc_decode_dev_workspace_bytes(const kvc_decode_params* p, int32_t tail_capacity);
+int kvc_decode_step_dev(const kvc_decode_params* p, int32_t tail_capacity,
+                        const int32_t* tail_rows_dev /* device, 1 int32 */,
+                        const int32_t* prefix_rows_b /* device [bsz], nullable: NULL = p->prefix_rows for every row */,
+                        const void* q, const void* k_new, const void* v_new,
+                        const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail,
+                        void* out, void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
+
 /* ---- decode-stage compression: re-compress the SPLIT decode cache in place (the reference's README TODO "Support KV cache
  * compression at decoding stage") ---------------------------------------------------------------------------------------------
  * The cache of one layer is the prefix [b][H_q][P][D] (per query head) and the tail [b][H_kv][T][D] (per KV head, the decoded

@@ -10,12 +10,15 @@ there is no CPU or eager-PyTorch fallback: if the extension is missing the impor
 """
 __version__ = "0.1.0"
 __all__ = ["QuantizedCompressedCache", "QuantizedCompressedLayer", "KVQuantCompressedCache", "KVQuantCompressedLayer",
-           "DecodeCompressedCache", "DecodeCompressedLayer", "HeavyHitterCache", "HeavyHitterLayer"]
+           "DecodeCompressedCache", "DecodeCompressedLayer", "HeavyHitterCache", "HeavyHitterLayer", "GraphDecoder"]
 
 
 def __getattr__(name):
     # the quantized, decode-compressed and heavy-hitter caches (cache.py) are exported lazily: importing the package does not
     # import transformers
+    if name == "GraphDecoder":                                # graph-replayed decoding (graph_decode.py)
+        from .graph_decode import GraphDecoder
+        return GraphDecoder
     if name in __all__:
         from . import cache
         return getattr(cache, name)

@@ -80,7 +80,16 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
     [rows[b], _stored) of row b are HOLES.  The fused step never reads them (kvc_decode_step_rows); the reference-shaped form
     hides them with the layer's own additive mask (`decode_mask`), not with a slice of the mask transformers built for the
     padded prompt.  `keys` / `values` are the padded view, `row_lengths()` says what is real.  When every row keeps the same
-    number of rows there are no holes and the layer is what it is for an unpadded batch."""
+    number of rows there are no holes and the layer is what it is for an unpadded batch.
+
+    DEVICE-LENGTH MODE (graph-replayed decoding, graph_decode.GraphDecoder; the plain layer type only): the SPLIT form with a tail
+    of FIXED capacity whose length lives in a device counter (int32 [1], shared by the layers of one cache) that the fused step
+    reads (kvc_decode_step_dev) — nothing the host passes to a step depends on the length, so a captured step replays while the
+    cache grows.  `_tail` / `true_length` are then the host's MIRROR of the counter: decode_attend advances them like any step
+    unless the owner of a graph holds them (`hold_mirror`) and advances them itself (`advance`) — during a replay no Python of
+    the layer runs.  The tail never re-allocates inside a step: `grow_tail` doubles it, an explicit host call between replays.
+    Everything that reads the layer (keys / values, lengths, masks, the batch operations, `update` / `_expand`, which leave the
+    mode) works from the mirror."""
 
     RESERVE = 256                       # spare rows allocated with the compressed prompt / tail rows allocated at a time
 
@@ -96,6 +105,14 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         self._holes = False             # the rows of the batch keep different numbers of prefix rows
         self._padded = False            # the prompt was a left-padded batch (prefill_rows): the layer masks its own decode steps
         self._pmax = 0                  # prefix rows per head the buffers hold (= _stored until `update` appends behind them)
+        self._leave_device_length()
+
+    def _leave_device_length(self):
+        self._devlen = False            # device-length mode: the tail's length is read from _dev_counter by the step
+        self._dev_counter = None        # int32 [1] on the device, shared by the layers of one cache; advanced by its owner
+        self._dev_ws = None             # this layer's own workspace of the step (a captured step cannot use the shared pool)
+        self._dev_ws_key = None
+        self._dev_hold = False          # the owner advances the mirror (`advance`), decode_attend does not
 
     # ---- the reference's view --------------------------------------------------------------------------------------
     # (`keys` / `values` are plain attributes of DynamicLayer; here they are computed from the buffers)
@@ -108,6 +125,7 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         self._kbuf = self._vbuf = self._ktail = self._vtail = self._rows = None
         self._stored = self._tail = self.true_length = self._pmax = 0
         self._split = self._holes = self._padded = False
+        self._leave_device_length()
 
     def _view(self, buf, tail):
         if buf is None:
@@ -161,6 +179,7 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         self._split, self._tail, self._ktail, self._vtail = False, 0, None, None
         self._rows, self._holes, self._padded, self._pmax = None, False, False, self._stored
         self.true_length = int(true_length)
+        self._leave_device_length()
 
     # ---- prefill of a left-padded batch: per-row lengths -----------------------------------------------------------------------
     def reserve_rows(self, bsz, n_heads, rows, head_dim, dtype, device, spare):
@@ -222,8 +241,9 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
     def _expand(self):
         """SPLIT -> EXPANDED (a caller wants plain H_q-head tensors to attend over)."""
         if self._split:
-            k, v = self.keys, self.values
+            k, v = self.keys, self.values                             # (device-length mode: the rows the mirror counts)
             self._split, self._tail, self._ktail, self._vtail = False, 0, None, None
+            self._leave_device_length()
             self._place(k, v, self.RESERVE)
 
     def update(self, key_states, value_states, *args, **kwargs):
@@ -251,6 +271,8 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         from . import _kvc
         t = key_states.shape[-2]
         b, hkv, _, d = key_states.shape
+        if self._devlen:
+            return self._decode_attend_dev(query_states, key_states, value_states, scaling)
         if not self._split:
             self._split, self._tail = True, 0
             self._ktail = torch.empty(b, hkv, self.RESERVE, d, dtype=key_states.dtype, device=key_states.device)
@@ -275,6 +297,77 @@ class CompressedDynamicLayer(_BatchOps, DynamicLayer):
         return out
 
     _batched_step = True                # bsz > 1 decode_attend calls go through kvc_decode_step_rows
+
+    # ---- decode: the fused step with the tail length on the device (graph replay) ------------------------------------------------
+    def enter_device_length(self, counter, capacity, n_kv_heads):
+        """Into device-length mode: a tail [bsz, n_kv_heads, capacity, D] of fixed capacity (the rows an earlier SPLIT tail holds
+        are copied) whose length the fused step reads from `counter` (int32 [1] on this layer's device).  The caller owns the
+        counter: it holds this layer's `_tail` now and is advanced, in stream order, after every step."""
+        if type(self) is not CompressedDynamicLayer:
+            raise NotImplementedError(f"kvcache_factory_amd: {type(self).__name__} has no device-length mode (graph-replayed decoding "
+                                      "covers the plain compressed cache only)")
+        if self._kbuf is None:
+            raise RuntimeError("kvcache_factory_amd: device-length mode needs a layer that went through a prefill")
+        if not self._split and self._stored != self._pmax:
+            raise NotImplementedError("kvcache_factory_amd: this layer already holds decoded rows in the reference-shaped form; enter "
+                                      "device-length mode right after the prefill")
+        assert counter.dtype == torch.int32 and counter.numel() == 1 and counter.device == self._kbuf.device
+        b, _, _, d = self._kbuf.shape
+        live = self._tail if self._split else 0
+        kt = torch.empty(b, n_kv_heads, max(int(capacity), live + 1), d, dtype=self._kbuf.dtype, device=self._kbuf.device)
+        vt = torch.empty_like(kt)
+        if live:
+            kt[:, :, :live].copy_(self._ktail[:, :, :live])
+            vt[:, :, :live].copy_(self._vtail[:, :, :live])
+        self._ktail, self._vtail, self._split, self._tail = kt, vt, True, live
+        self._devlen, self._dev_counter, self._dev_ws, self._dev_ws_key = True, counter, None, None
+
+    def tail_capacity(self):
+        return self._ktail.shape[2] if self._split else 0
+
+    def grow_tail(self):
+        """Device-length mode: a tail of twice the capacity with the live rows copied (host arithmetic on the mirror; no device
+        read).  Graphs captured over the old buffers are stale afterwards: the owner captures again."""
+        assert self._devlen
+        b, hkv, cap, d = self._ktail.shape
+        kt = torch.empty(b, hkv, 2 * cap, d, dtype=self._ktail.dtype, device=self._ktail.device)
+        vt = torch.empty_like(kt)
+        kt[:, :, :self._tail].copy_(self._ktail[:, :, :self._tail])
+        vt[:, :, :self._tail].copy_(self._vtail[:, :, :self._tail])
+        self._ktail, self._vtail, self._dev_ws, self._dev_ws_key = kt, vt, None, None
+
+    def hold_mirror(self, hold=True):
+        """The owner of a captured step advances the host mirror itself (`advance`): decode_attend then leaves it alone, so that
+        an eager step, a capture (which runs no kernel) and a replay (which runs no Python) keep the same books."""
+        self._dev_hold = bool(hold)
+
+    def advance(self, t):
+        """t rows were appended by a step whose Python did not count them (a replayed graph): the host mirror follows."""
+        self._tail += t
+        self.true_length += t
+
+    def _decode_attend_dev(self, query_states, key_states, value_states, scaling):
+        from . import _kvc
+        b, hkv, t, _ = key_states.shape
+        cap = self._ktail.shape[2]
+        if self._tail + t > cap:
+            raise RuntimeError(f"kvcache_factory_amd: the fixed tail holds {self._tail} of {cap} rows and the step brings {t}: "
+                               "grow_tail() first (device-length mode never re-allocates inside a step)")
+        key = (b, t, cap, query_states.stride(), key_states.stride())
+        if self._dev_ws_key != key:                                   # once per capacity: the step's own workspace
+            nbytes = _kvc.decode_dev_plan(query_states, key_states, self._kbuf, self._stored, self._ktail)[1]
+            self._dev_ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self._ktail.device)
+            self._dev_ws_key = key
+        rows = None
+        if self._holes:
+            if self._rows is None or self._rows.shape[0] != b:
+                self._rows = self.row_lengths()
+            rows = self._rows
+        out = _kvc.decode_step_dev(query_states, key_states, value_states, self._kbuf, self._vbuf, self._stored, self._ktail,
+                                   self._vtail, self._dev_counter, scaling, rows_b=rows, ws=self._dev_ws)
+        if not self._dev_hold:
+            self.advance(t)
+        return out
 
     def can_split(self):
         """The fused decode step needs the prefix in this layer's own buffers (a layer that went through prefill)."""

@@ -587,6 +587,67 @@ __attribute__((visibility("default"))) int kvc_decode_step_rows(const kvc_decode
                       hip_stream, prefix_rows_b, true);
 }
 
+// ---- the device-counted decode step (kvc_decode_dev.hip) ------------------------------------------------------------------
+namespace {
+int decode_dev_check(const kvc_decode_params* p, int32_t tail_capacity) {
+    if (!p) return fail(KVC_ERR_INVALID, "params is NULL");
+    kvc_decode_params c = *p;
+    c.tail_rows = 0;                                                  // ignored here: the device counts
+    if (int rc = decode_check(&c, nullptr)) return rc;
+    if (tail_capacity < p->new_rows) return fail(KVC_ERR_INVALID, "tail_capacity %d holds fewer rows than the step's new_rows %d", tail_capacity, p->new_rows);
+    if ((int64_t)p->prefix_rows + tail_capacity > 0x7fffffffLL) return fail(KVC_ERR_INVALID, "prefix_rows + tail_capacity overflows int32");
+    return KVC_OK;
+}
+}  // namespace
+
+__attribute__((visibility("default"))) size_t kvc_decode_dev_workspace_bytes(const kvc_decode_params* p, int32_t tail_capacity) {
+    if (decode_dev_check(p, tail_capacity)) return 0;
+    g_err[0] = 0;
+    const int rows = p->prefix_rows + tail_capacity;
+    return kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, kvc::decode_dev_splits(p->bsz, p->n_q_heads, p->new_rows, rows));
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_dev(const kvc_decode_params* p, int32_t tail_capacity, const int32_t* tail_rows_dev,
+                                                               const int32_t* prefix_rows_b, const void* q, const void* k_new, const void* v_new,
+                                                               const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail, void* out,
+                                                               void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = decode_dev_check(p, tail_capacity)) return rc;
+    if (!tail_rows_dev) return fail(KVC_ERR_INVALID, "tail_rows_dev is NULL");
+    if (((uintptr_t)tail_rows_dev) % 4) return fail(KVC_ERR_ALIGNMENT, "tail_rows_dev is not 4-byte aligned");
+    if (((uintptr_t)prefix_rows_b) % 4) return fail(KVC_ERR_ALIGNMENT, "prefix_rows_b is not 4-byte aligned");
+    if (!q || !k_new || !v_new || !k_tail || !v_tail || !out || (p->prefix_rows > 0 && (!k_prefix || !v_prefix)))
+        return fail(KVC_ERR_INVALID, "q, k_new, v_new, the tail, out (and the prefix when it has rows) must be non-NULL");
+    const int es = esize_of(p->dtype);
+    const void* ptrs[] = {q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, out, workspace};
+    for (const void* ptr : ptrs) if (((uintptr_t)ptr) % 16) return fail(KVC_ERR_ALIGNMENT, "a pointer is not 16-byte aligned");
+    const int64_t strides[] = {p->q_stride_b, p->q_stride_h, p->q_stride_l, p->new_stride_b, p->new_stride_h, p->new_stride_l,
+                               p->prefix_stride_b, p->prefix_stride_h, p->tail_stride_b, p->tail_stride_h,
+                               p->out_stride_b, p->out_stride_h, p->out_stride_l};
+    for (int64_t sd : strides) if ((sd * es) % 16) return fail(KVC_ERR_ALIGNMENT, "a stride is not a multiple of 16 bytes");
+    kvc::DecodeDevArgs da;
+    std::memset(&da, 0, sizeof(da));
+    kvc::DecodeArgs& a = da.a;
+    a.q = q; a.k_new = k_new; a.v_new = v_new; a.k_prefix = k_prefix; a.v_prefix = v_prefix; a.k_tail = k_tail; a.v_tail = v_tail; a.out = out;
+    a.q_stride_b = p->q_stride_b; a.q_stride_h = p->q_stride_h; a.q_stride_l = p->q_stride_l;
+    a.new_stride_b = p->new_stride_b; a.new_stride_h = p->new_stride_h; a.new_stride_l = p->new_stride_l;
+    a.prefix_stride_b = a.vprefix_stride_b = p->prefix_stride_b; a.prefix_stride_h = a.vprefix_stride_h = p->prefix_stride_h;
+    a.tail_stride_b = p->tail_stride_b; a.tail_stride_h = p->tail_stride_h;
+    a.out_stride_b = p->out_stride_b; a.out_stride_h = p->out_stride_h; a.out_stride_l = p->out_stride_l;
+    a.bsz = p->bsz; a.n_q_heads = p->n_q_heads; a.n_kv_heads = p->n_kv_heads; a.group = p->n_q_heads / p->n_kv_heads;
+    a.prefix_rows = p->prefix_rows; a.new_rows = p->new_rows;               // p->tail_rows is ignored: the device counts
+    a.esize = es; a.row_bytes = p->head_dim * es; a.scaling = p->scaling;
+    da.rows_b = prefix_rows_b; da.tail_dev = tail_rows_dev; da.tail_capacity = tail_capacity;
+    a.splits = 1;
+    if (workspace) {                                                  // as many splits of the BOUND as the workspace can hold
+        int s = kvc::decode_dev_splits(p->bsz, p->n_q_heads, p->new_rows, p->prefix_rows + tail_capacity);
+        while (s > 1 && kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, s) > workspace_bytes) --s;
+        a.splits = s; a.part = static_cast<float*>(workspace);
+    }
+    if (int rc = kvc::launch_decode_step_dev(da, p->dtype, p->head_dim, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no device-counted decode kernel for dtype %d head_dim %d", p->dtype, p->head_dim);
+    return hip_ok("device-counted decode step launch");
+}
+
 // ---- quantized decode cache (kvc_quant.hip) -------------------------------------------------------------------------------
 namespace {
 int quant_common(int dtype, int head_dim, int nbits, int group) {

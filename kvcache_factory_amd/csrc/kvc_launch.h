@@ -169,6 +169,13 @@ struct DecodeRowsArgs {    // kvc_decode_rows.hip: DecodeArgs (pruned_rows = 0) 
     const int32_t* rows_b;                            // [bsz], device
 };
 
+struct DecodeDevArgs {     // kvc_decode_dev.hip: DecodeArgs (pruned_rows = 0, tail_rows unused) + the lengths the device reads
+    DecodeArgs a;
+    const int32_t* rows_b;                            // [bsz], device, or null: a.prefix_rows for every batch row
+    const int32_t* tail_dev;                          // 1 int32, device: rows in the tail before this step
+    int tail_capacity;                                // rows the tail buffers hold (the clamp of the counter)
+};
+
 struct QuantArgs {         // kvc_quant.hip: quantize / de-quantize rows [row0, row0 + rows) of one segment (include/kvc.h layout)
     const void* src; void* dst;                       // [b][h][row][D] elements (quantize reads src, de-quantize writes dst)
     uint8_t* codes; const uint8_t* codes_in; float* meta; const float* meta_in;
@@ -279,6 +286,8 @@ int launch_decode_append(const DecodeArgs& a, hipStream_t st);                  
 int launch_decode_combine(const DecodeArgs& a, int dtype, int head_dim, hipStream_t st);   // splits -> out (kvc_decode.hip)
 int launch_decode_step_rows(DecodeRowsArgs a, int dtype, int head_dim, hipStream_t st);     // kvc_decode_rows.hip
 int decode_rows_splits(int bsz, int n_q_heads, int new_rows, int rows);
+int launch_decode_step_dev(DecodeDevArgs a, int dtype, int head_dim, hipStream_t st);       // kvc_decode_dev.hip
+int decode_dev_splits(int bsz, int n_q_heads, int new_rows, int rows);
 int launch_quantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_dequantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_decode_step_quant(DecodeQArgs a, int dtype, int head_dim, int nbits, const DecodeArgs& append, hipStream_t st);

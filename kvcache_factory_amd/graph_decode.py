@@ -1,0 +1,206 @@
+"""Graph-replayed decoding: one whole model step captured in a HIP graph and replayed for every generated token.
+
+A host-issued decode step costs more host time than kernel time (~24 us per layer for ~10 us of kernels).
+What kept a step from being captured was that the tail length was a host integer in the kernel arguments, the grid and the split
+plan.  kvc_decode_step_dev reads it on the device, the layers' device-length mode (cache.CompressedDynamicLayer) gives the tail a
+fixed capacity and a workspace of its own, and this class owns what is left: static input buffers, the device counter every
+layer reads, the capture, the host mirror of the lengths and the growth of the tails.
+
+    monkeypatch.replace_llama("snapkv")              # pyramidkv, streamingllm, h2o, l2norm, cam alike; replace_mistral too
+    dec = GraphDecoder(model, tail_rows=256)         # capture=False: the same kernels and books, issued eagerly
+    logits = dec.prefill(input_ids, attention_mask)  # eager, through the patched forwards
+    logits = dec.step(tokens)                        # tokens [bsz, 1] on the device -> the static logits buffer [bsz, 1, vocab]
+    out = dec.generate(input_ids, max_new_tokens=64) # greedy; argmax on the device, no host read per token
+
+The captured region is ONE chain on ONE stream: the model step, the copy of its logits into the static buffer and two in-graph
+`add_`s that advance the tail counter and the positions.  When the mirror says the tails are full, every layer's tail is doubled
+and the step is captured again: O(log n) captures, decided by host arithmetic.  `step` returns the static buffer — it is
+overwritten by the next step, so a caller who keeps logits clones them.
+"""
+import torch
+
+from . import pyramidkv_utils as pu
+from .cache import CompressedDynamicLayer, DecodeCompressedCache, HeavyHitterCache, QuantizedCompressedCache
+
+_OWN_LAYOUT = ("adakv", "headkv", "think")
+
+
+def _on_gpu(t):
+    return t.is_cuda
+
+
+def tails_needed(capacity, tail, t):
+    """How often a tail of `capacity` rows holding `tail` must double before a step of t rows fits (host arithmetic)."""
+    n = 0
+    while tail + t > capacity:
+        capacity, n = 2 * capacity, n + 1
+    return n
+
+
+class GraphDecoder:
+    WARMUP = 2                          # eager steps of the same code before a capture (lazy initialisations, workspaces, plans)
+
+    def __init__(self, model, tail_rows=256, capture=True):
+        if isinstance(tail_rows, bool) or not isinstance(tail_rows, int) or tail_rows < 1:
+            raise ValueError(f"tail_rows must be an int >= 1, got {tail_rows!r}")
+        self.model, self.tail_rows, self.capture = model, tail_rows, bool(capture)
+        self.config = model.config.get_text_config() if hasattr(model.config, "get_text_config") else model.config
+        self._refuse_model()
+        self.captures = 0               # graphs captured since the last prefill
+        self.grows = 0                  # times the tails were doubled since the last prefill
+        self._cache = self._graph = None
+        self._layers = ()
+        self._tok = self._pos = self._logits = self._counter = None
+
+    # ---- refusals: all raised before anything is stored or captured --------------------------------------------------------------
+    def _attn(self):
+        return self.model.model.layers[0].self_attn
+
+    def _refuse_model(self):
+        attn = self._attn()
+        method = getattr(type(attn).forward, "kvc_method", None)
+        if method is None:
+            raise NotImplementedError("kvcache_factory_amd: GraphDecoder needs a model whose attention was patched by "
+                                      "monkeypatch.replace_llama / replace_mistral before it was built; this model is unpatched "
+                                      "(fullkv keeps no compressed cache to decode over)")
+        if method in _OWN_LAYOUT:
+            raise NotImplementedError(f"kvcache_factory_amd: {method} keeps a cache layout of its own (ragged heads / pruned channels); "
+                                      "graph-replayed decoding covers the plain compressed cache only")
+        if getattr(self.config, "sliding_window", None) is not None:
+            raise NotImplementedError("kvcache_factory_amd: the fused decode step has no sliding window "
+                                      f"(sliding_window={self.config.sliding_window}); GraphDecoder cannot replay this model")
+        if getattr(self.config, "output_attentions", False):
+            raise NotImplementedError("kvcache_factory_amd: output_attentions needs the reference-shaped attention; the fused decode "
+                                      "step returns no weights, so GraphDecoder refuses it")
+        if attn.head_dim not in (64, 128):
+            raise NotImplementedError(f"kvcache_factory_amd: the decode kernels are built for head_dim 64 and 128, got {attn.head_dim}")
+        if self.model.training:
+            raise NotImplementedError("kvcache_factory_amd: GraphDecoder decodes in eval mode only (the fused step has no dropout)")
+        self.method = method
+
+    def _refuse_call(self, input_ids, cache):
+        for kind, why in ((QuantizedCompressedCache, "a quantized cache (QuantizedCompressedCache / KVQuantCompressedCache) quantizes "
+                                                     "its tail on a host-counted schedule"),
+                          (DecodeCompressedCache, "DecodeCompressedCache re-compresses on a host-counted schedule"),
+                          (HeavyHitterCache, "HeavyHitterCache evicts on a host-counted schedule")):
+            if isinstance(cache, kind):
+                raise NotImplementedError(f"kvcache_factory_amd: GraphDecoder replays the plain compressed cache only; {why}")
+        self._refuse_model()
+        if not pu.DECODE_KERNEL:
+            raise NotImplementedError("kvcache_factory_amd: KVC_DECODE_KERNEL=0 turns the fused decode step off; there is nothing for "
+                                      "GraphDecoder to replay")
+        if input_ids.dim() != 2:
+            raise ValueError("input_ids must be [bsz, length]")
+        if input_ids.shape[0] > 1 and not pu.BATCH_DECODE:
+            raise NotImplementedError("kvcache_factory_amd: KVC_BATCH_DECODE=0 turns the fused step off for batches; GraphDecoder "
+                                      f"cannot replay a batch of {input_ids.shape[0]}")
+        param = next(self.model.parameters())
+        if not _on_gpu(input_ids) or not _on_gpu(param):
+            raise NotImplementedError("kvcache_factory_amd: GraphDecoder runs on the GPU only (HIP kernels); got "
+                                      f"input_ids on {input_ids.device} and a model on {param.device}")
+        if param.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise NotImplementedError(f"kvcache_factory_amd: the decode kernels take bf16, fp16 and fp32, not {param.dtype}")
+
+    # ---- prefill -----------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prefill(self, input_ids, attention_mask=None, past_key_values=None):
+        """The prompt through the patched forwards (eager) on a fresh cache; every layer then goes into device-length mode with a
+        tail of `tail_rows`.  Left-padded batches as the patched forwards take them.  -> logits [bsz, 1, vocab] of the last token."""
+        from transformers import DynamicCache
+        from .attention import _pending_for
+        self._refuse_call(input_ids, past_key_values)
+        cache = DynamicCache(config=self.model.config) if past_key_values is None else past_key_values
+        if cache.get_seq_length() != 0:
+            raise RuntimeError("kvcache_factory_amd: GraphDecoder.prefill starts from an empty cache")
+        self._graph = self._cache = None
+        self._layers = ()
+        bsz, length = input_ids.shape
+        dev = input_ids.device
+        if attention_mask is None:
+            position_ids = None
+            pos = torch.full((bsz, 1), length, dtype=torch.long, device=dev)
+        else:
+            position_ids = (attention_mask.cumsum(-1) - 1).clamp(min=0)
+            pos = attention_mask.sum(-1, keepdim=True).to(torch.long)         # row b goes on from its own prompt's length
+        out = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, past_key_values=cache,
+                         use_cache=True, logits_to_keep=1)
+        _pending_for(cache).settle()
+        layers = tuple(cache.layers)
+        for layer in layers:
+            if type(layer) is not CompressedDynamicLayer or not layer.can_split():
+                raise NotImplementedError(f"kvcache_factory_amd: GraphDecoder found a {type(layer).__name__} in the cache after the "
+                                          "prefill; graph-replayed decoding covers the plain compressed cache only")
+        self._counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        for layer in layers:
+            layer.enter_device_length(self._counter, self.tail_rows, self.config.num_key_value_heads)
+            layer.hold_mirror(True)
+        self._cache, self._layers = cache, layers
+        self._tok = torch.zeros(bsz, 1, dtype=torch.long, device=dev)
+        self._pos = pos.contiguous()
+        self._logits = out.logits.clone()
+        self._tail, self._capacity = 0, layers[0].tail_capacity()
+        self.captures = self.grows = 0
+        return self._logits
+
+    # ---- one step ----------------------------------------------------------------------------------------------------------------
+    def _body(self):
+        """The step every variant runs: model over the static buffers, logits to the static buffer, counter and positions on."""
+        out = self.model(input_ids=self._tok, position_ids=self._pos, past_key_values=self._cache, use_cache=True)
+        self._logits.copy_(out.logits)
+        self._counter.add_(1)
+        self._pos.add_(1)
+
+    def _capture(self):
+        """WARMUP eager steps whose effect is taken back (the row they append at T is the row the real step overwrites; counter and
+        positions are set back on the device), then ONE capture of the same body on one stream."""
+        side = torch.cuda.Stream(self._tok.device)
+        side.wait_stream(torch.cuda.current_stream(self._tok.device))
+        with torch.cuda.stream(side):
+            for _ in range(self.WARMUP):
+                self._body()
+                self._counter.sub_(1)
+                self._pos.sub_(1)
+        torch.cuda.current_stream(self._tok.device).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._body()                                                     # (records only: nothing ran, nothing to take back)
+        self._graph = graph
+        self.captures += 1
+
+    def _grow(self):
+        for layer in self._layers:
+            layer.grow_tail()
+        self._capacity = self._layers[0].tail_capacity()
+        self._graph = None
+        self.grows += 1
+
+    @torch.no_grad()
+    def step(self, tokens):
+        """tokens [bsz, 1] (device) -> the static logits buffer [bsz, 1, vocab].  No host read; a graph replay when capture=True."""
+        if self._cache is None:
+            raise RuntimeError("kvcache_factory_amd: GraphDecoder.step before prefill")
+        for _ in range(tails_needed(self._capacity, self._tail, 1)):
+            self._grow()
+        self._tok.copy_(tokens.reshape(self._tok.shape))
+        if self.capture:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+        else:
+            self._body()
+        self._tail += 1
+        for layer in self._layers:                                           # the mirrors follow (no Python of the layers ran)
+            layer.advance(1)
+        return self._logits
+
+    @torch.no_grad()
+    def generate(self, input_ids, max_new_tokens, attention_mask=None):
+        """Greedy decoding: -> [bsz, length + max_new_tokens].  The argmax stays on the device; nothing is read per token."""
+        logits = self.prefill(input_ids, attention_mask)
+        out = [input_ids]
+        for j in range(max_new_tokens):
+            tok = logits[:, -1].argmax(-1, keepdim=True)
+            out.append(tok)
+            if j + 1 < max_new_tokens:
+                logits = self.step(tok)
+        return torch.cat(out, 1)
