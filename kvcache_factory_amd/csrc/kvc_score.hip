@@ -24,6 +24,7 @@
 namespace kvc {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));    // a staged 16-byte chunk (a native vector: stays in registers)
 
 __device__ __forceinline__ ScoreView view_of(const ScoreArgs& a, int item) {
     char* w = a.ws + (int64_t)item * a.ws_item_stride;
@@ -39,14 +40,26 @@ __device__ __forceinline__ ScoreView view_of(const ScoreArgs& a, int item) {
 
 // Diagnostic build only (-DKVC_STAMPS): per-wave s_memtime stamps at phase boundaries of logits_kernel, written to
 // a buffer of their own (ScoreArgs::dbg) that nothing else reads.  Never enabled in the shipped library.
+// logits kernels: slot 0 holds the wave's first stamp, slot p > 0 the ticks between stamp p and the stamp before it,
+// SUMMED over the wave's tiles (phase p is the interval that ENDS at stamp p), slot 7 the number of tiles.  The sums
+// stay in scalar registers and are stored once, at the end of the kernel: no store sits between the phases.
 #if defined(KVC_STAMPS)
+#define KVC_STAMP_DECL unsigned long long stamp_last_ = 0, stamp_sum_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
 #define KVC_STAMP(slot)                                                                                       \
     do {                                                                                                      \
         unsigned long long t_;                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");                          \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
-        if (a.dbg && lane == 0) a.dbg[((int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8 + (slot)] = t_; \
+        if ((slot) == 0) stamp_sum_[0] = t_; else stamp_sum_[slot] += t_ - stamp_last_;                       \
+        if ((slot) == 5) stamp_sum_[7] += 1;                                                                  \
+        stamp_last_ = t_;                                                                                     \
+    } while (0)
+#define KVC_STAMP_FLUSH                                                                                       \
+    do {                                                                                                      \
+        if (a.dbg && lane == 0)                                                                               \
+            for (int s_ = 0; s_ < 8; ++s_)                                                                    \
+                a.dbg[((int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 8 + s_] = stamp_sum_[s_]; \
     } while (0)
 #define KVC_SPSTAMP(slot)                                                                                     \
     do {                                                                                                      \
@@ -57,7 +70,9 @@ __device__ __forceinline__ ScoreView view_of(const ScoreArgs& a, int item) {
         if (a.dbg && threadIdx.x == 0 && blockIdx.y == 0) a.dbg[blockIdx.x * 8 + (slot)] = t_;                \
     } while (0)
 #else
+#define KVC_STAMP_DECL do { } while (0)
 #define KVC_STAMP(slot) do { } while (0)
+#define KVC_STAMP_FLUSH do { } while (0)
 #define KVC_SPSTAMP(slot) do { } while (0)
 #endif
 
@@ -202,39 +217,51 @@ __global__ __launch_bounds__(LOGITS_THREADS, 3) void logits_kernel(const ScoreAr
     const int wave_g = blockIdx.x * LOGITS_WAVES + wave, n_waves = gridDim.x * LOGITS_WAVES;
     char* const buf = tiles + wave * (32 * ROWP);
     const float sqrt_d = a.sqrt_d;
+    KVC_STAMP_DECL;
     KVC_STAMP(0);
 
     const char* const kbase = reinterpret_cast<const char*>(vw.k) +
                               ((int64_t)b * a.k_stride_b + (int64_t)g * a.k_stride_h) * ES;
     const int64_t tile_bytes = (int64_t)32 * a.k_stride_l * ES;    // one tile further along the key axis
-    uint32_t koff[STG];                                            // this lane's chunks inside a tile (global side)
+    // This lane's chunks inside a tile (global side): 32-bit byte offsets from the tile's uniform base, so that each load
+    // is `global_load_dwordx4 v, v_off, s[base]` with no per-lane 64-bit address arithmetic.
+    uint32_t koff[STG];
+    const uint32_t row_bytes = (uint32_t)(a.k_stride_l * ES);
+    auto set_koff = [&](int last_row) {                            // rows beyond last_row read row last_row instead
+        int r0 = lane / CH;
+        asm volatile("" : "+v"(r0));                               // the row numbers are formed here, not kept in registers
 #pragma unroll
-    for (int it = 0; it < STG; ++it) {
-        const int c = it * 64 + lane;
-        koff[it] = (uint32_t)((c / CH) * (a.k_stride_l * ES) + (c % CH) * 16);
-    }
-    auto issue = [&](int tile, uint4 (&st)[STG]) {
+        for (int it = 0; it < STG; ++it) {
+            const int c = it * 64 + lane, r = r0 + it * RPI;
+            uint32_t ro = (uint32_t)(r < last_row ? r : last_row) * row_bytes;
+            asm("" : "+v"(ro));                                    // a 32-bit multiply and an add: v_mad_u64_u32 would take a register pair
+            koff[it] = ro + (uint32_t)((c % CH) * 16);
+        }
+    };
+    // The next tile's loads are issued ahead of the MFMA chain and waited for only by commit(), after it: nothing on
+    // the way may need a vmcnt wait (tools/asm_audit.py: pipeline_stats pins that in the listing).  So the loads are
+    // unconditional.  A ragged tile — only the last of a head, and the last this wave touches in the M-tile — first
+    // clamps the offsets of its rows beyond the end onto row L - 1: no byte of a row >= L is read, and the columns so
+    // filled are never stored nor folded into a maximum (epilogue_general guards key < L; an MFMA column depends on
+    // its own key alone).  The M-tile loop sets koff afresh.
+    auto issue = [&](int tile, u32x4 (&st)[STG]) {
         const char* const tb = kbase + tile * tile_bytes;          // uniform
-        if (tile * 32 + 32 <= L) {
+        if (tile * 32 + 32 > L) set_koff(L - 1 - tile * 32);
 #pragma unroll
-            for (int it = 0; it < STG; ++it) st[it] = *reinterpret_cast<const uint4*>(tb + koff[it]);
-        } else {
-#pragma unroll
-            for (int it = 0; it < STG; ++it) {
-                const int key = tile * 32 + it * RPI + lane / CH;
-                st[it] = key < L ? *reinterpret_cast<const uint4*>(tb + koff[it]) : make_uint4(0, 0, 0, 0);
-            }
+        for (int it = 0; it < STG; ++it) {
+            asm volatile("" : "+v"(koff[it]));                     // keeps the zero-extension next to the load (SGPR-base form)
+            st[it] = *reinterpret_cast<const u32x4*>(tb + koff[it]);
         }
     };
     char* const cdst = buf + (lane / CH) * ROWP + (lane % CH) * 16;   // LDS side of the same chunks
-    auto commit = [&](const uint4 (&st)[STG]) {
+    auto commit = [&](const u32x4 (&st)[STG]) {
 #pragma unroll
         for (int it = 0; it < STG; ++it) {
             if constexpr (ASM_B) {
                 uint32_t* d = reinterpret_cast<uint32_t*>(cdst + it * (RPI * ROWP));
                 d[0] = st[it].x; d[1] = st[it].y; d[2] = st[it].z; d[3] = st[it].w;
             } else {
-                *reinterpret_cast<uint4*>(cdst + it * (RPI * ROWP)) = st[it];
+                *reinterpret_cast<u32x4*>(cdst + it * (RPI * ROWP)) = st[it];
             }
         }
     };
@@ -243,8 +270,9 @@ __global__ __launch_bounds__(LOGITS_THREADS, 3) void logits_kernel(const ScoreAr
         // ---- A operand: the workgroup converts the 32 query rows of this M-tile ONCE into an fp32 image in LDS, laid
         // out as the MFMA A-fragment of every lane (lane = row + 32*parity, value s = Q[row][2s + parity]), chunk-major
         // ([chunk][lane][4 values]) so that the waves read chunk c at one per-lane address + c*1024.
-        uint4 st[STG];
+        u32x4 st[STG];
         int tile = wave_g;
+        set_koff(31);
         if (tile < n_t) issue(tile, st);
         uint4 aq[FAST ? NSTEP : 1];                        // FAST: this lane's packed A fragments, chunk 2*s + kh of its row
         if constexpr (FAST) {
@@ -282,6 +310,12 @@ __global__ __launch_bounds__(LOGITS_THREADS, 3) void logits_kernel(const ScoreAr
         }
         if (!FAST) __syncthreads();
         if (tile < n_t) commit(st);
+        if constexpr (FAST) {
+            // the A fragments have landed before the tile loop: otherwise the first MFMA of every tile carries the
+            // wait for them, and that wait (vmcnt counts in order) would also cover the next tile's loads
+#pragma unroll
+            for (int sI = 0; sI < NSTEP; ++sI) asm volatile("" :: "v"(aq[sI].x));
+        }
         KVC_STAMP(1);
         float rm[16];                          // running maximum per accumulator register (row 8*(e/4) + 4*kh + e%4)
 #pragma unroll
@@ -397,9 +431,11 @@ __global__ __launch_bounds__(LOGITS_THREADS, 3) void logits_kernel(const ScoreAr
                 (void)pack2<DT>(x, back);                                         // first rounding
                 const f32x2 q = scale2_in_guard<D>(back, sqrt_d);                 // second: after the scaling
                 // (maximum before rounding: monotonic.)  One v_max_f32 each, spelled out: fmaxf() makes the compiler
-                // re-canonicalise all 16 running maxima at the top of every tile
-                asm("v_max_f32 %0, %1, %2" : "=v"(rm[e0]) : "v"(rm[e0]), "v"(q.x));
-                asm("v_max_f32 %0, %1, %2" : "=v"(rm[e0 + 1]) : "v"(rm[e0 + 1]), "v"(q.y));
+                // re-canonicalise all 16 running maxima at the top of every tile; updated in place.  (The register
+                // allocator still copies the 16 maxima where the plain and the general epilogue meet and at the loop's
+                // back edge; with "=v" outputs it is one set of copies fewer, but the prologue then spills 72 bytes.)
+                asm("v_max_f32 %0, %0, %1" : "+v"(rm[e0]) : "v"(q.x));
+                asm("v_max_f32 %0, %0, %1" : "+v"(rm[e0 + 1]) : "v"(q.y));
                 f32x2 unused;
                 pkw[(e0 >> 1) & 1] = pack2<DT>(q, unused);
                 if ((e0 & 3) == 2) *reinterpret_cast<uint2*>(lg + (soff[e0 >> 2] + pkeyoff)) = make_uint2(pkw[0], pkw[1]);
@@ -407,7 +443,8 @@ __global__ __launch_bounds__(LOGITS_THREADS, 3) void logits_kernel(const ScoreAr
         };
         for (; tile < n_t; tile += n_waves) {
             const int next = tile + n_waves;
-            if (next < n_t) issue(next, st);                  // in flight during the MFMAs below
+            u32x4 nx[STG];                                    // the next tile: in flight during the MFMAs below
+            if (next < n_t) issue(next, nx);
             __builtin_amdgcn_wave_barrier();
             KVC_STAMP(2);
             // ---- 32 rows x 32 keys, chain over d = 0..D-1 in order ----
@@ -460,7 +497,7 @@ __global__ __launch_bounds__(LOGITS_THREADS, 3) void logits_kernel(const ScoreAr
             asm volatile("" :: "v"(acc[0]), "v"(acc[15]));
             // the tile's LDS reads are all issued (the LDS serves a wave in order): the next tile may overwrite the single
             // buffer now, so its ds_writes overlap the VALU work that follows
-            if (next < n_t) commit(st);
+            if (next < n_t) commit(nx);
             KVC_STAMP(3);
             bool plain = rows_plain && tile * 32 + 32 <= L - W;
             if (plain) {
@@ -509,6 +546,8 @@ __global__ __launch_bounds__(LOGITS_THREADS, 3) void logits_kernel(const ScoreAr
         }
         __syncthreads();
     }
+    KVC_STAMP(6);
+    KVC_STAMP_FLUSH;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -552,6 +591,7 @@ __global__ __launch_bounds__(LOGITS_THREADS, 2) void logits_mt4_kernel(const Sco
     const int mt = wave;                      // this wave's M-tile: query rows 32 * wave .. + 31 (rows == 128)
     char* const img = smem + wave * IMG_BYTES;
     const float sqrt_d = a.sqrt_d;
+    KVC_STAMP_DECL;
     KVC_STAMP(0);
 
     const char* const kbase = reinterpret_cast<const char*>(vw.k) +
@@ -858,6 +898,8 @@ __global__ __launch_bounds__(LOGITS_THREADS, 2) void logits_mt4_kernel(const Sco
             }
         }
     }
+    KVC_STAMP(6);
+    KVC_STAMP_FLUSH;
 }
 
 // ---------------------------------------------------------------------------------------------

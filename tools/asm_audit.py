@@ -160,6 +160,60 @@ def loop_spans(body, first_line=0):
     return spans
 
 
+def _is_valu(op):
+    return op.startswith("v_") and not op.startswith("v_mfma")
+
+
+def pipeline_stats(body, first_line=0):
+    """Prefetch statistic of a K-scan kernel (logits_kernel): the next tile's global loads are issued ahead of the MFMA
+    chain and must stay in flight across it — their only wait is the commit's, after the chain.
+
+    The tile loop is the innermost loop that holds a v_mfma.  From its first `global_load` the full-tile path is
+    walked in program order the way a full tile runs it: an unconditional `s_branch` is followed, a conditional
+    branch falls through (the arms a compiler hangs on conditional branches there are the ragged / predicated ones),
+    up to the last v_mfma of the loop.  Reported: the `s_waitcnt vmcnt` instructions met on the way (`vm_waits`, listing
+    lines: must be empty — a wait there stalls the wave for an HBM round trip before its first MFMA), the global loads
+    and the VALU instructions on the path (`path_valu`), and the VALU instructions of the whole loop body, every arm
+    counted (`loop_valu`).  None if the kernel has no such loop."""
+    spans = [(a - first_line - 1, b - first_line - 1) for a, b in loop_spans(body, first_line)]
+    spans = [sp for sp in spans if any(ln.strip().startswith("v_mfma") for ln in body[sp[0]:sp[1] + 1])]
+    if not spans:
+        return None
+    lo, hi = min(spans, key=lambda sp: sp[1] - sp[0])
+    ops = {i: body[i].strip().split()[0] for i in range(lo, hi + 1)
+           if body[i].strip() and not body[i].strip().startswith((";", "."))}
+    loads = [i for i, op in ops.items() if op.startswith("global_load")]
+    mfmas = [i for i, op in ops.items() if op.startswith("v_mfma")]
+    out = {"tile_loop": (first_line + 1 + lo, first_line + 1 + hi), "loop_valu": sum(_is_valu(op) for op in ops.values()),
+           "path_loads": 0, "path_valu": 0, "vm_waits": [], "path_complete": False}
+    if not loads:
+        return out
+    labels = {m.group(1): i for i in range(lo, hi + 1) for m in [re.match(r"^(\.LBB\w+):", body[i].strip())] if m}
+    i, steps = loads[0], 0
+    while lo <= i <= hi and steps <= hi - lo:
+        steps += 1
+        op = ops.get(i)
+        if op is not None:
+            text = body[i].split(";", 1)[0]
+            if op == "s_waitcnt" and "vmcnt" in text:
+                out["vm_waits"].append(first_line + 1 + i)
+            elif op.startswith("global_load"):
+                out["path_loads"] += 1
+            elif _is_valu(op):
+                out["path_valu"] += 1
+            if i == mfmas[-1]:
+                out["path_complete"] = True
+                break
+            if op == "s_branch":
+                tgt = text.split()[1]
+                if tgt not in labels or labels[tgt] <= i:      # leaves the loop or goes back: not a path to the chain
+                    break
+                i = labels[tgt]
+                continue
+        i += 1
+    return out
+
+
 def audit_file(path, wanted=()):
     """{kernel: (problems, stats)} for every kernel of the listing that issues asm LDS loads (or is named in `wanted`)."""
     lines = open(path).read().split("\n")
@@ -178,6 +232,8 @@ def audit_file(path, wanted=()):
         inner = min(inner, key=lambda sp: sp[1] - sp[0]) if inner else None
         stats["tile_loop"] = inner
         stats["scratch_in_tile_loop"] = [n for n in stats["scratch_lines"] if inner and inner[0] <= n <= inner[1]]
+        if "logits_kernel" in name:
+            stats["pipeline"] = pipeline_stats(body, start)
         res[name] = (problems, stats)
     return res
 

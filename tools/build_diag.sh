@@ -15,7 +15,9 @@ B=$(mktemp -d)
 cd "$R/kvcache_factory_amd/csrc"
 FLAGS=$(make -s --eval 'pf:
 	@echo $(HIPFLAGS)' pf)
-for f in kvc_api kvc_score kvc_select kvc_select_exact kvc_gather kvc_h2o kvc_decode kvc_ragged kvc_l2norm kvc_merge kvc_think kvc_cam; do
+SRCS=$(make -s --eval 'ps:
+	@echo $(SRCS)' ps)                     # the library's own source list
+for f in ${SRCS//.hip/}; do
   /opt/rocm/bin/hipcc $FLAGS $FLAG -c $f.hip -o $B/$f.o &
 done
 wait
