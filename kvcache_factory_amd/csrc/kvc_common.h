@@ -60,14 +60,20 @@ template <> struct Dt<KVC_FP32> {
 template <int DT> __device__ __forceinline__ float rnd(float f) { return Dt<DT>::ld(Dt<DT>::st(f)); }
 
 // ---- exp: the reference's softmax exponent (torch Vectorized<float>::exp_u20) ----------------
+// From n = -125 up this is the header's sequence: p * 2^(n-1) * 2.  Below, 2^(n-1) has no normal encoding (the header's exponent
+// bits are 0 at n = -126, so every argument <= -87.0 would give +0) while torch.softmax underflows gradually down to 2^-149: there
+// p * 2^n is rounded ONCE into the subnormal — the host twin (oracle/kvc_oracle.cpp exp_u20) multiplies by 2^-64, exactly, then by
+// 2^(n+64) — and the lower clamp is -151 ln 2, the first argument whose result rounds to +0.  Here both cases are one v_ldexp_f32
+// (a correctly rounded p * 2^e, subnormal results included: the kernels keep fp32 subnormals) and one multiply:
+//     c = clamp(n + 126, 0, 1)            1 from n = -125 up, 0 below (n is integral)
+//     p = ldexp(p, n - c) * (1 + c)       p * 2^(n-1) rounded, then * 2   |   p * 2^n rounded, then * 1
 __device__ __forceinline__ float exp_u20(float x) {
-    const float ln_flt_min = u2f(0xc2aeac50u), ln_flt_max = u2f(0x42b17218u);
+    const float ln_sub_min = u2f(0xc2d15498u), ln_flt_max = u2f(0x42b17218u);
     const float log2ef = u2f(0x3fb8aa3bu), ln2f = u2f(0x3f317218u);
     const float c1 = 0.999999701f, c2 = 0.499991506f, c3 = 0.166676521f, c4 = 0.0418978221f,
                 c5 = 0.00828929059f;
-    const bool below = x < ln_flt_min;
     float s = (x < ln_flt_max) ? x : ln_flt_max;
-    s = (s > ln_flt_min) ? s : ln_flt_min;
+    s = (s > ln_sub_min) ? s : ln_sub_min;
     float fx = __builtin_fmaf(s, log2ef, 0.5f);
     fx = __builtin_floorf(fx);
     const float r = __builtin_fmaf(-fx, ln2f, s);
@@ -76,10 +82,9 @@ __device__ __forceinline__ float exp_u20(float x) {
     p = __builtin_fmaf(r, p, c2);
     p = __builtin_fmaf(r, p, c1);
     p = __builtin_fmaf(r, p, 1.0f);
-    const int n1 = (int)(fx - 1.0f);
-    const float two_n = below ? 0.0f : u2f((uint32_t)(n1 + 127) << 23);
-    p = p * two_n;
-    p = p * 2.0f;
+    const float c = __builtin_amdgcn_fmed3f(fx + 126.0f, 0.0f, 1.0f);
+    p = __builtin_amdgcn_ldexpf(p, (int)(fx - c));
+    p = p * (c + 1.0f);
     return p;
 }
 
@@ -87,13 +92,12 @@ __device__ __forceinline__ float exp_u20(float x) {
 // per-element IEEE operations, so each half is bit-identical to exp_u20 of that half).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 exp_u20x2(f32x2 x) {
-    const float ln_flt_min = u2f(0xc2aeac50u), ln_flt_max = u2f(0x42b17218u);
+    const float ln_sub_min = u2f(0xc2d15498u), ln_flt_max = u2f(0x42b17218u);
     const f32x2 log2ef = u2f(0x3fb8aa3bu), nln2f = -u2f(0x3f317218u);
     const f32x2 c1 = 0.999999701f, c2 = 0.499991506f, c3 = 0.166676521f, c4 = 0.0418978221f, c5 = 0.00828929059f;
-    const bool below0 = x.x < ln_flt_min, below1 = x.y < ln_flt_min;
     f32x2 s;
-    s.x = (x.x < ln_flt_max) ? x.x : ln_flt_max; s.x = (s.x > ln_flt_min) ? s.x : ln_flt_min;
-    s.y = (x.y < ln_flt_max) ? x.y : ln_flt_max; s.y = (s.y > ln_flt_min) ? s.y : ln_flt_min;
+    s.x = (x.x < ln_flt_max) ? x.x : ln_flt_max; s.x = (s.x > ln_sub_min) ? s.x : ln_sub_min;
+    s.y = (x.y < ln_flt_max) ? x.y : ln_flt_max; s.y = (s.y > ln_sub_min) ? s.y : ln_sub_min;
     f32x2 fx = __builtin_elementwise_fma(s, log2ef, (f32x2)0.5f);
     fx.x = __builtin_floorf(fx.x); fx.y = __builtin_floorf(fx.y);
     const f32x2 r = __builtin_elementwise_fma(fx, nln2f, s);          // fma(-fx, ln2, s): negating an operand is exact
@@ -102,26 +106,24 @@ __device__ __forceinline__ f32x2 exp_u20x2(f32x2 x) {
     p = __builtin_elementwise_fma(r, p, c2);
     p = __builtin_elementwise_fma(r, p, c1);
     p = __builtin_elementwise_fma(r, p, (f32x2)1.0f);
-    const f32x2 fm1 = fx - (f32x2)1.0f;
-    f32x2 two_n;
-    two_n.x = below0 ? 0.0f : u2f((uint32_t)((int)fm1.x + 127) << 23);
-    two_n.y = below1 ? 0.0f : u2f((uint32_t)((int)fm1.y + 127) << 23);
-    p = p * two_n;
-    p = p * (f32x2)2.0f;
+    f32x2 c = fx + (f32x2)126.0f;
+    c.x = __builtin_amdgcn_fmed3f(c.x, 0.0f, 1.0f); c.y = __builtin_amdgcn_fmed3f(c.y, 0.0f, 1.0f);
+    const f32x2 e = fx - c;
+    p.x = __builtin_amdgcn_ldexpf(p.x, (int)e.x); p.y = __builtin_amdgcn_ldexpf(p.y, (int)e.y);
+    p = p * (c + (f32x2)1.0f);
     return p;
 }
 
-// exp_u20x2 for arguments <= 0 (a logit minus its row maximum), bit-identical to it there with 10 instructions fewer (17 for two
-// values): one v_med3 clamps to [ln(FLT_MIN), 0]; the clamped lower bound yields fx = -126 and so 2^n = bits 0 = +0.0 — what the
-// `below` select of exp_u20x2 returns — and (int)(fx - 1) + 127 = (int)fx + 126 because fx is integral.  An argument > 0 can only
-// come from a lane whose result is discarded (a key or row beyond L, padded with zeros): it is treated as 0.
+// exp_u20x2 for arguments <= 0 (a logit minus its row maximum), bit-identical to it there: one v_med3 clamps to [-151 ln 2, 0], and
+// the clamped lower bound yields n = -151, whose p * 2^-151 rounds to +0.0.  An argument > 0 can only come from a lane
+// whose result is discarded (a key or row beyond L, padded with zeros): it is treated as 0.
 __device__ __forceinline__ f32x2 exp_u20x2_nonpos(f32x2 x) {
-    const float ln_flt_min = u2f(0xc2aeac50u);
+    const float ln_sub_min = u2f(0xc2d15498u);
     const f32x2 log2ef = u2f(0x3fb8aa3bu), nln2f = -u2f(0x3f317218u);
     const f32x2 c1 = 0.999999701f, c2 = 0.499991506f, c3 = 0.166676521f, c4 = 0.0418978221f, c5 = 0.00828929059f;
     f32x2 s_;
-    s_.x = __builtin_amdgcn_fmed3f(x.x, ln_flt_min, 0.0f);
-    s_.y = __builtin_amdgcn_fmed3f(x.y, ln_flt_min, 0.0f);
+    s_.x = __builtin_amdgcn_fmed3f(x.x, ln_sub_min, 0.0f);
+    s_.y = __builtin_amdgcn_fmed3f(x.y, ln_sub_min, 0.0f);
     f32x2 fx = __builtin_elementwise_fma(s_, log2ef, (f32x2)0.5f);
     fx.x = __builtin_floorf(fx.x); fx.y = __builtin_floorf(fx.y);
     const f32x2 r = __builtin_elementwise_fma(fx, nln2f, s_);
@@ -130,11 +132,11 @@ __device__ __forceinline__ f32x2 exp_u20x2_nonpos(f32x2 x) {
     p = __builtin_elementwise_fma(r, p, c2);
     p = __builtin_elementwise_fma(r, p, c1);
     p = __builtin_elementwise_fma(r, p, (f32x2)1.0f);
-    f32x2 two_n;
-    two_n.x = u2f((uint32_t)((int)fx.x + 126) << 23);
-    two_n.y = u2f((uint32_t)((int)fx.y + 126) << 23);
-    p = p * two_n;
-    p = p * (f32x2)2.0f;
+    f32x2 c = fx + (f32x2)126.0f;
+    c.x = __builtin_amdgcn_fmed3f(c.x, 0.0f, 1.0f); c.y = __builtin_amdgcn_fmed3f(c.y, 0.0f, 1.0f);
+    const f32x2 e = fx - c;
+    p.x = __builtin_amdgcn_ldexpf(p.x, (int)e.x); p.y = __builtin_amdgcn_ldexpf(p.y, (int)e.y);
+    p = p * (c + (f32x2)1.0f);
     return p;
 }
 

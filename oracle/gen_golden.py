@@ -448,6 +448,9 @@ def cases():
     add("l2norm_8k_bf16", method="l2norm", layer_idx=5, dtype="bf16", Hq=32, Hkv=8, L=8000, D=128, cap=128, seed=0)
     add("l2norm_8k_bf16_cap4096", method="l2norm", layer_idx=5, dtype="bf16", Hq=32, Hkv=8, L=8000, D=128, cap=4096, seed=0)
     add("l2norm_32k_bf16", method="l2norm", layer_idx=5, dtype="bf16", Hq=8, Hkv=2, L=32000, D=128, cap=4096, seed=0)
+    # ---- logits spread over more than 87 nats: softmax results in the fp32-subnormal band, a selection that reaches exact zeros ----
+    add("edge_bf16_deep_underflow", dtype="bf16", L=257, cap=200, W=8, scale_q=160.0, seed=501)
+    add("edge_fp32_deep_underflow", dtype="fp32", L=257, cap=200, W=8, scale_q=160.0, seed=502)
     return cs
 
 

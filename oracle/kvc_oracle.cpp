@@ -116,15 +116,19 @@ template <class DT> static inline float rnd(float f) { return DT::ld(DT::st(f));
 // clamp, n = floor(x*log2e + 0.5), r = x - n*ln2, degree-5 Horner with FMAs, scale by 2^(n-1)
 // then by 2.  Every step is a single IEEE fp32 operation, so the gfx950 kernel can (and does)
 // execute the identical sequence.
+// Below n = -125 the header's 2^(n-1) has no normal encoding (its exponent bits are 0 at n = -126:
+// everything <= -87.0 would become +0), while torch.softmax itself underflows gradually down to
+// 2^-149 (DESIGN.md §4 "Scoring stage over the logit range").  There 2^n is applied as 2^-64, which
+// is exact, then 2^(n+64), which rounds once into the subnormal; the lower clamp is -151 ln 2, the
+// first argument whose result rounds to +0.  From n = -125 up the sequence is the header's, unchanged.
 // ----------------------------------------------------------------------------------------
 static inline float exp_u20(float x) {
-    const float ln_flt_min = u2f(0xc2aeac50u), ln_flt_max = u2f(0x42b17218u);
+    const float ln_sub_min = u2f(0xc2d15498u), ln_flt_max = u2f(0x42b17218u);   // -151 ln 2, ln(FLT_MAX)
     const float log2ef = u2f(0x3fb8aa3bu), ln2f = u2f(0x3f317218u);
     const float c1 = 0.999999701f, c2 = 0.499991506f, c3 = 0.166676521f, c4 = 0.0418978221f,
                 c5 = 0.00828929059f;
-    const bool below = x < ln_flt_min;
     float s = (x < ln_flt_max) ? x : ln_flt_max;      // _mm512_min_ps(values, max)
-    s = (s > ln_flt_min) ? s : ln_flt_min;            // _mm512_max_ps(src, min)
+    s = (s > ln_sub_min) ? s : ln_sub_min;            // _mm512_max_ps(src, min), the bound moved down
     float fx = std::fmaf(s, log2ef, 0.5f);
     fx = std::floor(fx);
     const float r = std::fmaf(-fx, ln2f, s);
@@ -133,10 +137,10 @@ static inline float exp_u20(float x) {
     p = std::fmaf(r, p, c2);
     p = std::fmaf(r, p, c1);
     p = std::fmaf(r, p, 1.0f);
-    const int n1 = (int)(fx - 1.0f);
-    const float two_n = below ? 0.0f : u2f((uint32_t)(n1 + 127) << 23);
-    p = p * two_n;
-    p = p * 2.0f;
+    const int n = (int)fx;                            // -151 .. 128
+    const int e1 = n < -125 ? -64 : n - 1, e2 = n < -125 ? n + 64 : 1;
+    p = p * u2f((uint32_t)(e1 + 127) << 23);
+    p = p * u2f((uint32_t)(e2 + 127) << 23);
     return p;
 }
 
@@ -780,6 +784,9 @@ KVCO_API int kvco_think_prune(const kvco_params* P, const void* q, const void* k
 
 // Scalar probes used by tests to pin the helper arithmetic.
 KVCO_API float kvco_exp_u20(float x) { return exp_u20(x); }
+KVCO_API void kvco_exp_u20_array(const float* x, int64_t n, float* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = exp_u20(x[i]);
+}
 KVCO_API float kvco_sum(const float* x, int64_t n, int sum_mode) {
     (void)sum_mode;
     return sum_torch16(x, n);

@@ -66,6 +66,7 @@ def lib():
         L.kvco_pyramid_k.restype = ctypes.c_int64
         L.kvco_exp_u20.argtypes = [ctypes.c_float]
         L.kvco_exp_u20.restype = ctypes.c_float
+        L.kvco_exp_u20_array.argtypes = [vp, ctypes.c_int64, vp]
         L.kvco_sum.argtypes = [vp, ctypes.c_int64, ctypes.c_int]
         L.kvco_sum.restype = ctypes.c_float
         L.kvco_f32_to_f16.argtypes = [ctypes.c_float]
@@ -124,6 +125,14 @@ def scores(q, k, window, kernel_size=5, pooling="avgpool", full_rows=False, want
         ws = torch.empty(H, n, dtype=q.dtype)
     _rc(lib().kvco_scores(ctypes.byref(p), _ptr(q), _ptr(k), _ptr(lg), _ptr(pr), _ptr(ws), _ptr(out)), "scores")
     return (out, lg, pr, ws) if want_intermediates else out
+
+
+def exp_u20(x):
+    """The oracle's softmax exponential on a contiguous fp32 CPU tensor, elementwise."""
+    assert x.dtype == torch.float32 and x.device.type == "cpu" and x.is_contiguous()
+    out = torch.empty_like(x)
+    lib().kvco_exp_u20_array(_ptr(x), x.numel(), _ptr(out))
+    return out
 
 
 def topk(scores_t, n_keep, tie_mode=TIES_TORCH, n_threads=0):
