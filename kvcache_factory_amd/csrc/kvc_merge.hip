@@ -14,7 +14,7 @@
 //   merge_kept_kernel     the normalised kept keys of every head, fp32 in the workspace             (one wave per row)
 //   merge_pivot_kernel    the cosines on the f32 MFMA (32 dropped tokens per wave x 128 kept rows per LDS stage; 64
 //                         v_mfma_f32_32x32x2_f32 per block = the d-ascending fp32 chain: products of two 16-bit values are exact
-//                         in fp32), rounded to the dtype, first maximum
+//                         in fp32), rounded to the dtype, first maximum (NaN above every number, like torch.max)
 //   merge_reduce_kernel   one wave per (head, kept row) for K and V together: walks the pivots 64 at a time (ballot -> ascending order), adds the
 //                         merged rows in fp32, then sum -> dtype, count -> dtype, quotient -> dtype
 // Arithmetic = oracle/kvc_oracle.cpp kvco_merge_pivot (norms in torch's 8-accumulator order, fp32 divides, one rounding each),
@@ -113,8 +113,15 @@ __global__ __launch_bounds__(64) void merge_kept_kernel(const MergeArgs a) {
 // its token j, normalised, in 64 registers); the kept rows are the A operand, 64 rows at a time through LDS (de-interleaved:
 // [row][kh][s], so that four steps of a lane are one 16-byte read).  64 MFMAs per 32 x 32 block of cosines = the d-ascending
 // fp32 chain (each MFMA adds its two products in k order; products of two 16-bit values are exact in fp32), at twice the
-// rate of the scalar FMA; the first maximum over the kept rows is taken with an explicit (value, smaller row) rule.
+// rate of the scalar FMA; the first maximum over the kept rows is taken with an explicit (value, smaller row) rule in which a
+// NaN cosine is the largest value (first_max).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+// torch.max's order on a row of cosines: a NaN is above every number and NaNs are equal among themselves, so the first NaN
+// column wins, else the first maximal one.  (A key row of zeros normalises to 0 / 0: a whole NaN column, or a whole NaN row.)
+__device__ __forceinline__ bool first_max(float v, int r, float bestv, int best) {
+    if (v != v) return bestv == bestv || r < best;
+    return v > bestv || (v == bestv && r < best);
+}
 constexpr int MP_STAGE = 64;                               // kept rows per LDS stage: 33 KB, four workgroups per CU
 constexpr int MP_PITCH = 132;                              // floats per kept row in LDS (16-byte reads of a quarter wave: all banks)
 template <int DT>
@@ -188,14 +195,14 @@ __global__ __launch_bounds__(256) void merge_pivot_kernel(const MergeArgs a) {
             for (int e = 0; e < 16; ++e) {
                 const int r = r0 + mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
                 const float v = rnd<DT>(acc[e]);
-                if (r < a.rows && (best == 0x7fffffff || v > bestv || (v == bestv && r < best))) { best = r; bestv = v; }
+                if (r < a.rows && (best == 0x7fffffff || first_max(v, r, bestv, best))) { best = r; bestv = v; }
             }
         }
     }
     {   // the two half-waves hold different kept rows of the same token: first maximum of the pair
         const float ov = xor_lane<32>(bestv);
         const int orow = __float_as_int(xor_lane<32>(__int_as_float(best)));
-        if (orow != 0x7fffffff && (best == 0x7fffffff || ov > bestv || (ov == bestv && orow < best))) { best = orow; bestv = ov; }
+        if (orow != 0x7fffffff && (best == 0x7fffffff || first_max(ov, orow, bestv, best))) { best = orow; bestv = ov; }
     }
     if (live && kh == 0) a.pivot[hb * a.q_len + p] = best;
 }

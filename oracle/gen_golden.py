@@ -227,6 +227,42 @@ def run_merge_case(c):
     return meta, out
 
 
+def run_merge_stage_case(c):
+    """merge_kv called directly (pyramidkv_utils.py:119-170) on a spec of tests/stage_ref.py — keys with zero rows (NaN cosines) or one
+    tight cluster (hundreds of merges into one kept row), and the spec's own indices, since no top-k would select them.  Stored as in
+    run_merge_case: the indices, the pivot captured at similarity.max, the number of dropped tokens, the merged K / V and their SHA-256."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stage_ref
+    spec = next(s for s in stage_ref.GRID if s.name == c["stage_spec"])
+    x = stage_ref.inputs(spec)
+    k, v, idx = stage_ref.expand(spec, x["k"]), stage_ref.expand(spec, x["v"]), x["idx"]
+    taps = []
+    orig_max = torch.Tensor.max
+
+    def tmax(t, *a, **kwa):
+        r = orig_max(t, *a, **kwa)
+        if a or kwa:
+            taps.append(r.indices.detach().clone())
+        return r
+    torch.Tensor.max = tmax
+    try:
+        t0 = time.time()
+        with contextlib.redirect_stdout(io.StringIO()):
+            ko, vo = ref.merge_kv(k, v, idx[None, :, :, None].expand(1, spec.Hq, spec.n_keep, spec.D), spec.W, "pivot")
+        dt = time.time() - t0
+    finally:
+        torch.Tensor.max = orig_max
+    meta = dict(c)
+    meta.update(Hq=spec.Hq, Hkv=spec.Hkv, L=spec.L, D=spec.D, W=spec.W, cap=spec.n_keep + spec.W, n_keep=spec.n_keep, seed=spec.seed)
+    meta["ref_seconds"] = round(dt, 4)
+    meta["passthrough"] = False
+    meta["out_shape"] = list(ko.shape)
+    meta["k_out_sha256"], meta["v_out_sha256"] = sha(ko), sha(vo)
+    meta["drop_len"] = int(taps[-1].shape[-1])
+    return meta, {"indices": idx.numpy().astype(np.int64), "pivot": taps[-1][0].numpy().astype(np.int16),
+                  "k_out": raw_bits(ko[0]), "v_out": raw_bits(vo[0])}
+
+
 def run_all_layers_case(c):
     """PyramidKV over EVERY layer of the model (the schedule of pyramidkv_utils.py:205-215 gives each layer its own budget, and
     with it a different libstdc++ regime / tie-group cut): one input, n_layers reference runs.  Stored per layer: the indices
@@ -451,6 +487,9 @@ def cases():
     # ---- logits spread over more than 87 nats: softmax results in the fp32-subnormal band, a selection that reaches exact zeros ----
     add("edge_bf16_deep_underflow", dtype="bf16", L=257, cap=200, W=8, scale_q=160.0, seed=501)
     add("edge_fp32_deep_underflow", dtype="fp32", L=257, cap=200, W=8, scale_q=160.0, seed=502)
+    # ---- merge_kv itself on two regimes of tests/stage_ref.py (zero key rows planted per head: NaN cosines whose first column lies in the upper half-wave, the second M-tile, a later LDS stage; one cluster: counts beyond 256) ----
+    add("merge_snapkv_bf16_zero_rows_L700", method="merge_snapkv", dtype="bf16", stage_spec="zero_rows-planted-bf16-D128-H4x2-L700-W8-k136")
+    add("merge_snapkv_bf16_clustered_L300", method="merge_snapkv", dtype="bf16", stage_spec="clustered-bf16-D128-H4x2-L300-W8-k3")
     return cs
 
 
@@ -473,6 +512,8 @@ def main():
             meta, arrays = run_l2norm_case(c)
         elif c["method"] == "think":
             meta, arrays = run_think_case(c)
+        elif c.get("stage_spec"):
+            meta, arrays = run_merge_stage_case(c)
         elif c["method"].startswith("merge_"):
             meta, arrays = run_merge_case(c)
         elif c["method"] == "cam":

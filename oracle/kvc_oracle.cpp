@@ -627,7 +627,9 @@ KVCO_API int kvco_l2norm(const kvco_params* P, const void* k, const void* v, voi
 //     not documented; restated as the d-ascending fp32 sum of the (exact) products, rounded once — on 230 400 entries 10
 //     differed from torch (0.004 %) and no argmax moved; at the 8k configuration a handful of dropped tokens may pick a
 //     different pivot than the reference (measured by the fixtures);
-//   max(dim=-1): the FIRST maximal column;  merged = ((dropped + kept[pivot]) -> dtype) / 2;
+//   max(dim=-1): the FIRST maximal column, a NaN cosine (a key row of zeros normalises to 0 / 0) above every number and equal
+//     to every other NaN — torch.max on the CPU returns the first NaN column, and column 0 of an all-NaN row;
+//   merged = ((dropped + kept[pivot]) -> dtype) / 2;
 //   scatter_reduce(mean, include_self=True): fp32 sum of the row itself and its merged rows in ascending dropped position,
 //     rounded to the dtype; the count (1 + contributions) rounded to the dtype; their quotient rounded to the dtype.
 // ----------------------------------------------------------------------------------------
@@ -686,7 +688,7 @@ static int merge_pivot_impl(const kvco_params& P, const void* k_, const void* v_
                 float s = 0.0f;
                 for (int d = 0; d < D; ++d) s = s + a[(size_t)d] * kn[(size_t)r * D + d];
                 s = rnd<DT>(s);
-                if (r == 0 || s > bestv) { best = r; bestv = s; }
+                if (r == 0 || (std::isnan(s) ? !std::isnan(bestv) : s > bestv)) { best = r; bestv = s; }
             }
             if (pivot_out) pivot_out[(int64_t)h * M + p] = (int32_t)best;
             const raw* ksel = kh + kpos[(size_t)best] * P.k_stride_l;

@@ -38,6 +38,12 @@ def _make_qkv_cached(Hq, Hkv, L, D, dtype, seed, peaky, expanded, device):
 
 def inputs(meta, device="cpu", expanded=True):
     """Regenerate (q, k, v) of a fixture exactly as oracle/gen_golden.py fed them to the reference."""
+    if meta.get("stage_spec"):                              # a spec of stage_ref.py fed to the reference's merge_kv itself
+        import stage_ref
+        spec = next(s for s in stage_ref.GRID if s.name == meta["stage_spec"])
+        x = stage_ref.inputs(spec)
+        k, v = (x["k"], x["v"]) if not expanded else (stage_ref.expand(spec, x["k"]), stage_ref.expand(spec, x["v"]))
+        return x["q"].to(device), k.to(device), v.to(device)
     dtype = DT[meta["dtype"]]
     q, k, v = _make_qkv_cached(meta["Hq"], meta["Hkv"], meta["L"], meta["D"], dtype, meta["seed"],
                                meta.get("peaky", False), expanded, device)
