@@ -110,7 +110,10 @@ typedef struct kvc_params {
                                   logits twice instead of the 16-rows-per-workgroup form that reads them once (identical results).
                                   Bit13 (testing): tie_mode torch_cpu with every budget in the one-wave heap's regime (16-bit,
                                   1 <= k <= 128, k * 64 <= q_len - window): the separate selection and gather launches instead of
-                                  the kernel that copies K / V rows as the selection finalises them (identical results). */
+                                  the kernel that copies K / V rows as the selection finalises them (identical results).
+                                  Bit14 (measurement): the window-8 stage with its exponentials kept in registers, one workgroup
+                                  per CU, instead of the form that recomputes them in its second pass so that two heads share a
+                                  CU (identical results). */
     int32_t dot_mode;          /* kvc_dot_mode */
     int64_t q_stride_b, q_stride_h, q_stride_l;   /* element strides of q[b][h][l][:] */
     int64_t k_stride_b, k_stride_h, k_stride_l;

@@ -1516,6 +1516,222 @@ __global__ __launch_bounds__(SP_THREADS) void softmax_pool_ws_kernel(const Score
 }
 
 // ---------------------------------------------------------------------------------------------
+// softmax_pool_pair_kernel (W = 8, 16-bit dtypes, rows up to 8 064 keys): softmax_pool_ws_kernel with a register footprint
+// small enough that TWO workgroups — two heads — are resident on a CU, so that one head's loads, barriers and chain adds
+// run under the other's arithmetic.  softmax_pool_ws_kernel keeps the exponentials of pass 1 for pass 2 (72 VGPRs) next to
+// the raw logits they came from (36 VGPRs): 110 VGPRs x 16 waves, one workgroup per CU, nothing resident to fill its waits.
+// Here pass 2 recomputes exp_u20x2_nonpos(x - m) from the raw logits the thread still holds — a deterministic function of
+// the same operands, so the same bits — and the row maxima / reciprocals, which are the same in every lane, are handed to
+// the compiler as wave-uniform values (v_readfirstlane: SGPR operands of the packed ops).  Everything else is
+// softmax_pool_ws_kernel: 128 chain threads (row tid / 16, chain tid % 16), THREADS - 128 workers, stage boundaries at
+// multiples of 16 keys, one barrier per stage reached by every thread; no persistence, no communication between workgroups.
+// With two heads on a CU the stage is bound by VALU issue, not by waiting (DESIGN.md §4 "Two heads per CU"): recomputing
+// alone gives back what the overlap gains, so the exponential also sheds the part of its tail that is exact for arguments
+// >= -86 (exp_nonpos_tail_normal below) — with that the stage is faster than softmax_pool_ws_kernel.
+//   THREADS = 1024: 896 workers x 9 stages, 62 VGPRs (8 waves per SIMD), 59 904 B of LDS: the geometry that is launched.
+//   THREADS =  512: 384 workers x 21 stages, <= 128 VGPRs (4 waves per SIMD), 33 792 B of LDS: measured slower, not instantiated.
+// grid = (bsz*n_q_heads, items), block = THREADS.
+// ---------------------------------------------------------------------------------------------
+template <int THREADS> struct PairGeom {
+    static constexpr int WORK = THREADS - WS_CHAIN;                      // worker threads = keys per stage (a multiple of 128)
+    static constexpr int ITERS = (WS_ITERS * WS_WORK + WORK - 1) / WORK; // stages that cover 8 064 keys
+    static constexpr int PITCH = WORK + 16;                              // stage row pitch (floats): rows 16 banks apart
+    static constexpr int STAGE = 8 * PITCH;
+    static constexpr int BODY = 2 * STAGE > WS_ITERS * WS_WORK ? 2 * STAGE : WS_ITERS * WS_WORK;   // stages (pass 1) / per-key sums (pass 2)
+    static constexpr size_t LDS = (size_t)(64 + 64 + 256 + BODY) * sizeof(float);
+    static constexpr int WAVES_PER_SIMD = 2 * (THREADS / 64) / 4;        // two workgroups on the CU's four SIMDs
+    static_assert(WORK % 128 == 0 && PITCH % 64 == 16, "stage boundaries at multiples of 16 keys; chain reads conflict-free");
+    static_assert(2 * LDS <= 160 * 1024, "two workgroups' LDS must fit a CU's 160 KiB");
+    static_assert(2 * (THREADS / 64) <= 32, "two workgroups' waves must fit a CU's 32");
+};
+// exp_u20x2_nonpos (kvc_common.h) in two steps — exp_nonpos_tail(exp_nonpos_clamp(x)) is that function, operation for operation —
+// and the tail for clamped arguments >= -86 (n = floor(s log2 e + 0.5) >= -124), where its two-step scaling is exact:
+// 12582912 + n holds n in its low mantissa bits, and shifted by 23 it is n in the exponent field (the rest shifts out).
+__device__ __forceinline__ f32x2 exp_nonpos_clamp(f32x2 x) {
+    const float ln_sub_min = u2f(0xc2d15498u);
+    f32x2 s_;
+    s_.x = __builtin_amdgcn_fmed3f(x.x, ln_sub_min, 0.0f);
+    s_.y = __builtin_amdgcn_fmed3f(x.y, ln_sub_min, 0.0f);
+    return s_;
+}
+__device__ __forceinline__ f32x2 exp_nonpos_poly(f32x2 s_, f32x2& fx) {
+    const f32x2 log2ef = u2f(0x3fb8aa3bu), nln2f = -u2f(0x3f317218u);
+    const f32x2 c1 = 0.999999701f, c2 = 0.499991506f, c3 = 0.166676521f, c4 = 0.0418978221f, c5 = 0.00828929059f;
+    fx = __builtin_elementwise_fma(s_, log2ef, (f32x2)0.5f);
+    fx.x = __builtin_floorf(fx.x); fx.y = __builtin_floorf(fx.y);
+    const f32x2 r = __builtin_elementwise_fma(fx, nln2f, s_);
+    f32x2 p = __builtin_elementwise_fma(r, c5, c4);
+    p = __builtin_elementwise_fma(r, p, c3);
+    p = __builtin_elementwise_fma(r, p, c2);
+    p = __builtin_elementwise_fma(r, p, c1);
+    return __builtin_elementwise_fma(r, p, (f32x2)1.0f);
+}
+__device__ __forceinline__ f32x2 exp_nonpos_tail(f32x2 s_) {
+    f32x2 fx;
+    f32x2 p = exp_nonpos_poly(s_, fx);
+    f32x2 c = fx + (f32x2)126.0f;
+    c.x = __builtin_amdgcn_fmed3f(c.x, 0.0f, 1.0f); c.y = __builtin_amdgcn_fmed3f(c.y, 0.0f, 1.0f);
+    const f32x2 e = fx - c;
+    p.x = __builtin_amdgcn_ldexpf(p.x, (int)e.x); p.y = __builtin_amdgcn_ldexpf(p.y, (int)e.y);
+    return p * (c + (f32x2)1.0f);
+}
+__device__ __forceinline__ f32x2 exp_nonpos_tail_normal(f32x2 s_) {
+    f32x2 fx;
+    const f32x2 p = exp_nonpos_poly(s_, fx);
+    const f32x2 t = fx + (f32x2)12582912.0f;
+    return f32x2{u2f((f2u(t.x) << 23) + f2u(p.x)), u2f((f2u(t.y) << 23) + f2u(p.y))};
+}
+__device__ __forceinline__ float wave_uniform(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+template <int DT, int THREADS>
+__global__ __launch_bounds__(THREADS, PairGeom<THREADS>::WAVES_PER_SIMD) void softmax_pool_pair_kernel(const ScoreArgs a) {
+    typedef PairGeom<THREADS> G;
+    const ScoreView vw = view_of(a, blockIdx.y);
+    typedef typename Dt<DT>::raw raw;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int W = 8;
+    static_assert((W * (int)sizeof(raw)) == 16, "one 16-byte vector per key");
+    const int tid = threadIdx.x, hb = blockIdx.x;
+    const bool worker = tid >= WS_CHAIN;
+    const int wt = tid - WS_CHAIN;
+    const int L = a.q_len, n = L - W;
+    const int iters = (L + G::WORK - 1) / G::WORK;
+    float* const m = reinterpret_cast<float*>(smem);              // [64]
+    float* const rinv = m + 64;                                   // [64]
+    float* const scratch = rinv + 64;                             // [256]
+    float* const stage = scratch + 256;                           // [2][STAGE] (pass 1)
+    float* const seg = stage;                                     // [<= 8064]  (pass 2)
+    const raw* const lg = reinterpret_cast<const raw*>(vw.logits) + (int64_t)hb * L * W;
+    // a key beyond L reads the row's last key instead: neither the chains (which stop at L) nor the pooling (which stops at
+    // n) read what becomes of it, so no pass carries a per-stage lane mask
+    uint4 rawx[G::ITERS];
+#pragma unroll
+    for (int it = 0; it < G::ITERS; ++it) {
+        const int key = it * G::WORK + wt;
+        rawx[it] = make_uint4(0, 0, 0, 0);
+        if (worker && it < iters) rawx[it] = *reinterpret_cast<const uint4*>(lg + (int64_t)(key < L ? key : L - 1) * W);
+    }
+    block_row_max(vw.pmax + (int64_t)hb * a.n_tiles * W, a.n_tiles, W, m, scratch);
+    f32x2 nm[W / 2];                                              // minus the row maxima, in pairs (wave-uniform)
+#pragma unroll
+    for (int w = 0; w < W / 2; ++w) nm[w] = f32x2{-wave_uniform(m[2 * w]), -wave_uniform(m[2 * w + 1])};
+    // The 8 exponentials of one key.  exp_u20x2_nonpos ends in ldexp(p, n - c) * (c + 1) with c = clamp(n + 126, 0, 1), the
+    // reference's two-step scaling that rounds twice into the subnormals.  For n >= -124 that is p * 2^n exactly (c = 1, both
+    // steps exact), i.e. n added to p's exponent field.  A wave whose 64 x 4 clamped arguments all lie in [-86, 0] (n >= -124)
+    // takes that shorter tail — a quarter of the function's instructions, and both passes of a head run it; any other wave runs
+    // the function as it stands.  (Clamped arguments are <= 0: as unsigned words a larger one is a more negative argument.)
+    auto exps = [&](const uint4& rx, f32x2 (&e)[W / 2]) {
+        const uint32_t wv[4] = {rx.x, rx.y, rx.z, rx.w};
+#pragma unroll
+        for (int h = 0; h < W / 2; h += 2) {                      // four rows at a time: the clamped arguments wait in registers
+            uint32_t far = 0;
+#pragma unroll
+            for (int w = h; w < h + 2; ++w) {
+                const f32x2 x = f32x2{Dt<DT>::ld((uint16_t)(wv[w] & 0xffffu)), Dt<DT>::ld((uint16_t)(wv[w] >> 16))};
+                e[w] = exp_nonpos_clamp(x + nm[w]);               // x + (-m) == x - m
+                far = max(far, max(f2u(e[w].x), f2u(e[w].y)));
+            }
+            if (__builtin_amdgcn_ballot_w64(far > 0xc2ac0000u /* -86.0f */) == 0) {
+                e[h] = exp_nonpos_tail_normal(e[h]); e[h + 1] = exp_nonpos_tail_normal(e[h + 1]);
+            } else {
+                e[h] = exp_nonpos_tail(e[h]); e[h + 1] = exp_nonpos_tail(e[h + 1]);
+            }
+        }
+    };
+    // pass 1: the workers' exponentials go to LDS stage by stage; the chain waves add them in torch's order
+    const int cw = tid >> 4, cl = tid & 15;                       // chain threads: row cw, chain cl
+    float acc = 0.0f;
+#pragma unroll
+    for (int it = 0; it < G::ITERS; ++it) {
+        if (it < iters) {                                          // (uniform)
+            float* buf = stage + (it & 1) * G::STAGE;
+            if (worker) {
+                f32x2 e[W / 2];
+                exps(rawx[it], e);
+#pragma unroll
+                for (int w = 0; w < W / 2; ++w) {
+                    buf[(2 * w) * G::PITCH + wt] = e[w].x;
+                    buf[(2 * w + 1) * G::PITCH + wt] = e[w].y;
+                }
+            }
+            __syncthreads();       // stage `it` is complete; the chain waves finished stage it - 1 before they arrived here, so
+                                   // the workers may overwrite that buffer's twin (stage it + 1) while stage `it` is being added
+            if (!worker) {
+                const float* row = buf + cw * G::PITCH + cl;
+                const int cnt = (L - it * G::WORK - cl + 15) >> 4;     // keys it * WORK + cl + 16 i < L
+                if (cnt >= G::WORK / 16) {
+                    float va[8], vb[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) va[i] = row[16 * i];
+#pragma unroll
+                    for (int b = 0; b < G::WORK / 16 / 8; ++b) {       // blocks of 8 terms, the next block's reads in flight
+                        float (&cur)[8] = (b & 1) ? vb : va;
+                        float (&nxt)[8] = (b & 1) ? va : vb;
+                        if (b + 1 < G::WORK / 16 / 8) {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) nxt[i] = row[16 * (8 * (b + 1) + i)];
+                        }
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) acc = acc + cur[i];
+                    }
+                } else {
+                    for (int i = 0; i < cnt; ++i) acc = acc + row[16 * i];
+                }
+            }
+        }
+    }
+    const float sum = chain16_fold(acc);
+    if (!worker && cl == 0) {
+        rinv[cw] = 1.0f / sum;
+        vw.rowmax[(int64_t)hb * W + cw] = m[cw];
+        vw.rowsum[(int64_t)hb * W + cw] = sum;
+    }
+    __syncthreads();                                              // rinv visible; the stages are free for the per-key sums
+    f32x2 ri[W / 2];
+#pragma unroll
+    for (int w = 0; w < W / 2; ++w) ri[w] = f32x2{wave_uniform(rinv[2 * w]), wave_uniform(rinv[2 * w + 1])};
+    // pass 2: the same exponentials again from the raw logits; p = round(e / sum), window sum (cascade), round -> LDS
+#pragma unroll
+    for (int it = 0; it < G::ITERS; ++it) {
+        if (it < iters && worker) {
+            f32x2 e[W / 2];
+            exps(rawx[it], e);
+            CascadeSum cs;
+            cs.init(W);
+#pragma unroll
+            for (int w = 0; w < W / 2; ++w) {
+                const f32x2 pr = e[w] * ri[w];
+                cs.add(rnd<DT>(pr.x));
+                cs.add(rnd<DT>(pr.y));
+            }
+            seg[it * G::WORK + wt] = rnd<DT>(a.window_mean ? cs.result() / (float)W : cs.result());   // (keys >= n: within seg, not read)
+        }
+    }
+    __syncthreads();
+    const int pad = a.pooling == KVC_POOL_NONE ? 0 : a.kernel_size / 2;
+    raw* const out = reinterpret_cast<raw*>(vw.scores) + (int64_t)hb * n;
+    for (int jo = tid; jo < n; jo += THREADS) {
+        float c;
+        if (a.pooling == KVC_POOL_NONE) {
+            c = seg[jo];
+        } else {
+            const int lo = jo - pad < 0 ? 0 : jo - pad;
+            const int hi = jo - pad + a.kernel_size > n ? n : jo - pad + a.kernel_size;
+            if (a.pooling == KVC_POOL_MAX) {
+                c = -__builtin_inff();
+                for (int i = lo; i < hi; ++i) { const float v = seg[i]; c = v > c ? v : c; }
+            } else {
+                float s2 = 0.0f;
+                for (int i = lo; i < hi; ++i) s2 = s2 + seg[i];
+                c = rnd<DT>(s2 / (float)a.kernel_size);
+            }
+        }
+        out[jo] = Dt<DT>::st(c);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // softmax_rows16_kernel + softmax_comb16_kernel (round 3; W = 16, 32 or 64, 16-bit dtypes, 16 <= L <= 8 192): the logits are
 // read ONCE.  softmax_pool_kernel cannot keep a head's exponentials at these windows (32 rows x 8 keys per thread) and reads
 // the logits a second time for its normalising pass: 1.02 GB fetched for 524 MB of logits at C2 / W = 32 (round 2's PMC pass).
@@ -1695,6 +1911,14 @@ static void launch_softmax_pool_t(const ScoreArgs& a, hipStream_t st) {
             }
             if constexpr (WV == 8) {                          // chain waves beside worker waves (debug_stage_mask bit 10: round 2's form)
                 if (a.q_len >= 1024 && a.q_len <= WS_ITERS * WS_WORK && !(a.stage_mask & (256 | 1024))) {
+                    if constexpr (DT != KVC_FP32) {           // two heads per CU (bit 14: the form that keeps its exponentials)
+                        if (!(a.stage_mask & 16384)) {
+                            static LdsCache c_pair = {};
+                            (void)ensure_lds(reinterpret_cast<const void*>(&softmax_pool_pair_kernel<DT, 1024>), PairGeom<1024>::LDS, c_pair);
+                            hipLaunchKernelGGL((softmax_pool_pair_kernel<DT, 1024>), g, dim3(1024), PairGeom<1024>::LDS, st, a);
+                            return;
+                        }
+                    }
                     static LdsCache c_ws = {};
                     (void)ensure_lds(reinterpret_cast<const void*>(&softmax_pool_ws_kernel<DT>), kSoftmaxLds, c_ws);
                     hipLaunchKernelGGL((softmax_pool_ws_kernel<DT>), g, dim3(SP_THREADS), kSoftmaxLds, st, a);
