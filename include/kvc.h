@@ -281,6 +281,25 @@ int kvc_decode_step_dev(const kvc_decode_params* p, int32_t tail_capacity,
                         const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail,
                         void* out, void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
 
+/* kvc_decode_step_dev_ring: kvc_decode_step_dev that also RECORDS THE STEP'S QUERIES in a ring, so that a later kvc_decode_compress
+ * finds the window's queries without a launch of its own.  q_ring [b][H_q][ring_rows][D] (rows dense, ring_stride_b / ring_stride_h in
+ * elements), ring_rows = W >= 1.  With T the clamped counter value the step reads (above),
+ *     query row i of the step is copied byte for byte to ring slot (T + i) % W, for every i >= new_rows - W;
+ * older rows of the step are not recorded, so every slot has at most one writer in a call, and slots the step does not own are not
+ * touched.  A kvc_decode_compress with ring_start = T_end % W, T_end the tail rows at that moment (>= W, all appended through this
+ * entry), then finds window row w at slot (ring_start + w) % W.  The ring must not overlap any other tensor of the call.
+ * Everything else is kvc_decode_step_dev's contract word for word — the clamp, the plan of the bound, the workspace
+ * (kvc_decode_dev_workspace_bytes), the checks before any pointer is used, enqueue-only — and the call issues as many kernels: the ring
+ * rows are written by the launch that appends K / V.  ring_rows < 1, a NULL or misaligned q_ring, a ring stride that is not a
+ * multiple of 16 bytes or is smaller than the ring's extent: KVC_ERR_INVALID. */
+int kvc_decode_step_dev_ring(const kvc_decode_params* p, int32_t tail_capacity,
+                             const int32_t* tail_rows_dev /* device, 1 int32 */,
+                             const int32_t* prefix_rows_b /* device [bsz], nullable */,
+                             const void* q, const void* k_new, const void* v_new,
+                             const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail, void* out,
+                             void* q_ring, int32_t ring_rows, int64_t ring_stride_b, int64_t ring_stride_h,
+                             void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
+
 /* ---- decode-stage compression: re-compress the SPLIT decode cache in place (the reference's README TODO "Support KV cache
  * compression at decoding stage") ---------------------------------------------------------------------------------------------
  * The cache of one layer is the prefix [b][H_q][P][D] (per query head) and the tail [b][H_kv][T][D] (per KV head, the decoded

@@ -32,7 +32,8 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_dequantize_rows_outliers", "kvc_decode_quant_outliers_workspace_bytes", "kvc_decode_step_quant_outliers",
            "kvc_decode_compress_workspace_bytes", "kvc_decode_compress", "kvc_decode_rows_workspace_bytes",
            "kvc_decode_step_rows", "kvc_decode_scored_workspace_bytes", "kvc_decode_step_scored",
-           "kvc_decode_evict_workspace_bytes", "kvc_decode_evict", "kvc_decode_dev_workspace_bytes", "kvc_decode_step_dev")
+           "kvc_decode_evict_workspace_bytes", "kvc_decode_evict", "kvc_decode_dev_workspace_bytes", "kvc_decode_step_dev",
+           "kvc_decode_step_dev_ring")
 
 
 class KvcError(RuntimeError):
@@ -169,6 +170,8 @@ def lib():
         L.kvc_decode_dev_workspace_bytes.argtypes = [ctypes.POINTER(DecodeParams), ctypes.c_int32]
         L.kvc_decode_dev_workspace_bytes.restype = sz
         L.kvc_decode_step_dev.argtypes = [ctypes.POINTER(DecodeParams), ctypes.c_int32] + [vp] * 11 + [sz, vp]
+        L.kvc_decode_step_dev_ring.argtypes = [ctypes.POINTER(DecodeParams), ctypes.c_int32] + [vp] * 11 + [
+            ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp, sz, vp]
         L.kvc_select_workspace_bytes.argtypes = [pp]
         L.kvc_select_workspace_bytes.restype = sz
         L.kvc_l2norm_workspace_bytes.argtypes = [pp]
@@ -518,8 +521,12 @@ def decode_step_dev(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_
     Nothing passed to the library depends on T, so a captured call replays for every later length.  ws: a caller-owned uint8
     workspace of at least decode_dev_plan(...)[1] bytes and out: a caller-owned [b, t, H_q, D] buffer — a captured call must own
     both (the shared pool may be replaced by a later call); without them the call uses the pool and a fresh tensor."""
-    _require_gpu(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, tail_counter, rows_b)
-    dev = _one_device(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, tail_counter, rows_b, ws, out)
+    return _decode_step_dev(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_counter, scaling, rows_b, ws, out, None)
+
+
+def _decode_step_dev(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_counter, scaling, rows_b, ws, out, ring):
+    _require_gpu(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, tail_counter, rows_b, ring)
+    dev = _one_device(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, tail_counter, rows_b, ws, out, ring)
     q, k_new, v_new = _last_dim_contig(q), _last_dim_contig(k_new), _last_dim_contig(v_new)
     if k_new.stride() != v_new.stride():        # K comes out of RoPE contiguous, V is the projection's transposed view
         k_new, v_new = k_new.contiguous(), v_new.contiguous()
@@ -541,10 +548,26 @@ def decode_step_dev(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_
         ws = workspace(dev, nbytes) if nbytes else None
     else:
         assert ws.dtype == torch.uint8 and ws.is_contiguous()
-    _check(_call(dev, lib().kvc_decode_step_dev, ctypes.byref(p), k_tail.shape[2], _ptr(tail_counter), _ptr(rows_b), _ptr(q), _ptr(k_new),
-                 _ptr(v_new), _ptr(k_prefix), _ptr(v_prefix), _ptr(k_tail), _ptr(v_tail), _ptr(out), _ptr(ws),
-                 ws.numel() if ws is not None else 0, _stream(dev)))
+    args = (ctypes.byref(p), k_tail.shape[2], _ptr(tail_counter), _ptr(rows_b), _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(k_prefix),
+            _ptr(v_prefix), _ptr(k_tail), _ptr(v_tail), _ptr(out))
+    tail = (_ptr(ws), ws.numel() if ws is not None else 0, _stream(dev))
+    if ring is None:
+        _check(_call(dev, lib().kvc_decode_step_dev, *args, *tail))
+    else:
+        assert ring.dtype == q.dtype and ring.shape[:2] == (b, hq) and ring.shape[3] == D and ring.stride(3) == 1 and ring.stride(2) == D
+        _check(_call(dev, lib().kvc_decode_step_dev_ring, *args, _ptr(ring), ring.shape[2], ring.stride(0), ring.stride(1), *tail))
     return out
+
+
+def decode_step_dev_ring(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_counter, scaling, ring, rows_b=None,
+                         ws=None, out=None):
+    """decode_step_dev that also records the step's queries (kvc_decode_step_dev_ring): with T the clamped counter value the step
+    reads, query row i goes byte for byte to slot (T + i) % W of ring [b, H_q, W, D] (rows dense) for i >= t - W; no other slot is
+    touched.  The same number of launches: the append's launch writes the ring rows.  A later decode_compress with
+    ring_start = (tail rows then) % W finds the window in the ring."""
+    if ring is None:
+        raise KvcError(ERR_INVALID, "decode_step_dev_ring needs a ring")
+    return _decode_step_dev(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_counter, scaling, rows_b, ws, out, ring)
 
 
 def decode_compress_params(method, ring, k_prefix, prefix_rows, k_tail, tail_rows, out, window, n_keep, kernel_size=5,

@@ -408,6 +408,27 @@ def _check_interval(interval):
 DECODE_METHODS = ("snapkv", "pyramidkv", "streamingllm")   # the patched forwards that have a decode-time rule
 
 
+def decode_budget(cluster, interval):
+    """(method, B, W) of a layer compressed at decode time for `cluster` (the patched forward's kv_cluster): the one statement of
+    the budget rule, shared by DecodeCompressedLayer and BoundedDeviceLayer."""
+    from . import _kvc
+    W = cluster.window_size
+    method = cluster._method
+    if method not in (_kvc.SNAPKV, _kvc.PYRAMIDKV, _kvc.STREAMINGLLM) or getattr(cluster, "merge", None) is not None:
+        raise NotImplementedError(f"kvcache_factory_amd: DecodeCompressedCache has no decode-time rule for {type(cluster).__name__}"
+                                  f" (merge={getattr(cluster, 'merge', None)!r})")
+    if interval < W:
+        raise ValueError(f"DecodeCompressedCache: interval {interval} must be >= window_size {W}")
+    if method == _kvc.PYRAMIDKV:
+        return method, cluster._budget(2 * cluster.max_capacity_prompt) + W, W
+    return method, cluster.max_capacity_prompt, W
+
+
+def decode_trigger(P, T, B, W, interval):
+    """The one statement of the trigger: a layer holding P prefix rows and T decoded rows after a step compresses now."""
+    return P + T >= B + interval and T >= W
+
+
 class DecodeCompressedLayer(CompressedDynamicLayer):
     """A CompressedDynamicLayer whose decoded rows are compressed again, so that the layer stays bounded during long generations.
 
@@ -467,17 +488,7 @@ class DecodeCompressedLayer(CompressedDynamicLayer):
 
     def budget(self, cluster):
         """(method, B, W) of this layer for `cluster` (the patched forward's kv_cluster)."""
-        from . import _kvc
-        W = cluster.window_size
-        method = cluster._method
-        if method not in (_kvc.SNAPKV, _kvc.PYRAMIDKV, _kvc.STREAMINGLLM) or getattr(cluster, "merge", None) is not None:
-            raise NotImplementedError(f"kvcache_factory_amd: DecodeCompressedCache has no decode-time rule for {type(cluster).__name__}"
-                                      f" (merge={getattr(cluster, 'merge', None)!r})")
-        if self.interval < W:
-            raise ValueError(f"DecodeCompressedCache: interval {self.interval} must be >= window_size {W}")
-        if method == _kvc.PYRAMIDKV:
-            return method, cluster._budget(2 * cluster.max_capacity_prompt) + W, W
-        return method, cluster.max_capacity_prompt, W
+        return decode_budget(cluster, self.interval)
 
     def after_decode(self, cluster, query_states):
         from . import _kvc
@@ -488,7 +499,7 @@ class DecodeCompressedLayer(CompressedDynamicLayer):
         S, t = P + T, query_states.shape[-2]
         if method != _kvc.STREAMINGLLM and S > B + self.interval - W:
             self._ring_write(query_states, S - t, W)
-        if S >= B + self.interval and T >= W:
+        if decode_trigger(P, T, B, W, self.interval):
             self._compress(cluster, method, B, W, P, T)
 
     def _ring_write(self, q, r0, W):
@@ -565,6 +576,150 @@ class DecodeCompressedCache(Cache):
         text = config.get_text_config() if hasattr(config, "get_text_config") else config
         self.interval = interval
         super().__init__(layers=[DecodeCompressedLayer(interval) for _ in range(text.num_hidden_layers)])
+
+
+def bounded_tail_rows(P0, B, interval):
+    """Rows the fixed tail of a BoundedDeviceLayer needs with one-token steps: the layer compresses at the first step after which
+    P + T >= B + interval and T >= W (decode_trigger; interval >= W).  From the prefill's P0 rows that is T = B + interval - P0
+    (or W <= interval when the prefill kept more than that); from then on P = B and it is T = interval."""
+    return max(interval, B + interval - P0)
+
+
+class BoundedDeviceLayer(CompressedDynamicLayer):
+    """Decode-stage compression in DEVICE-LENGTH MODE (graph_decode.GraphDecoder(model, interval=N)): DecodeCompressedLayer's budget
+    and trigger (decode_budget, decode_trigger) on a layer whose every address is fixed for the whole generation, so that ONE captured
+    step replays however long it runs.  One sequence (bsz = 1), one-token steps.
+
+    The K / V prefix buffers hold Pcap = max(P0, B) rows per query head (the prefill's P0 rows are copied in); how many of them are
+    in use is a device int32 (`_plen`) the step reads as its per-row prefix length.  The tail holds bounded_tail_rows(P0, B,
+    interval) rows and its length lives in this layer's own device counter (PyramidKV layers compress on different steps).  The
+    step (kvc_decode_step_dev_ring) also records its query in the W-slot ring, row T at slot T % W; StreamingLLM keeps no ring and
+    takes kvc_decode_step_dev.  The step's workspace and the two B-row output buffers of a compression are allocated on entry.
+
+    `_stored` / `_tail` / `true_length` are the host MIRROR, advanced by the owner (`advance`), who then calls `maybe_compress`:
+    when the mirror says so, kvc_decode_compress runs eagerly on the step's stream over (P, T) with ring_start = T % W into the
+    output buffers, a device copy moves the B rows back into the fixed prefix buffers, and the prefix-length word (B) and the
+    counter (0) are set by device ops.  Nothing is read from the device.  `after_decode` does nothing here."""
+
+    def __init__(self, interval=128):
+        _check_interval(interval)
+        super().__init__()
+        self.interval = interval
+        self._clear_bounded()
+
+    def _clear_bounded(self):
+        self._plen = None                   # int32 [1] on the device: prefix rows in use (the step's prefix_rows_b)
+        self._qring = None                  # [1, H_q, W, D]: the query of tail row T at slot T % W (None: StreamingLLM)
+        self._kout = self._vout = None      # [1, H_q, B, D]: where a compression writes before the rows are copied back
+        self._plan = None                   # (method, B, W)
+        self._cluster = None
+        self.compressions = 0
+
+    def reset(self):
+        super().reset()
+        self._clear_bounded()
+
+    def prefill(self, *a, **kw):
+        raise NotImplementedError("kvcache_factory_amd: a BoundedDeviceLayer is made from a prefilled layer (BoundedDeviceLayer.adopt)")
+
+    @classmethod
+    def adopt(cls, layer, cluster, interval, counter, n_kv_heads):
+        """The bounded layer that takes over from `layer`, a plain CompressedDynamicLayer right after its prefill (its P0 rows are
+        copied).  counter: int32 [1] on the layer's device, this layer's own; it is set to 0 here by a device op."""
+        if type(layer) is not CompressedDynamicLayer or layer._kbuf is None:
+            raise NotImplementedError(f"kvcache_factory_amd: BoundedDeviceLayer adopts a prefilled CompressedDynamicLayer, not a "
+                                      f"{type(layer).__name__}")
+        if layer._split or layer._stored != layer._pmax or layer._devlen:
+            raise NotImplementedError("kvcache_factory_amd: this layer already holds decoded rows; enter the bounded mode right after "
+                                      "the prefill")
+        b, hq, _, d = layer._kbuf.shape
+        if b != 1 or layer._padded:
+            raise NotImplementedError(f"kvcache_factory_amd: decode-stage compression holds one sequence (bsz = 1), got a batch of {b}")
+        self = cls(interval)
+        method, B, W = self._plan = decode_budget(cluster, interval)
+        assert counter.dtype == torch.int32 and counter.numel() == 1 and counter.device == layer._kbuf.device
+        from . import _kvc
+        P0, dt, dev = layer._stored, layer._kbuf.dtype, layer._kbuf.device
+        self.dtype, self.device, self.is_initialized = layer.dtype, layer.device, True
+        self.true_length = layer.true_length
+        self._kbuf = torch.empty(1, hq, max(P0, B), d, dtype=dt, device=dev)
+        self._vbuf = torch.empty_like(self._kbuf)
+        self._kbuf[:, :, :P0].copy_(layer._kbuf[:, :, :P0])
+        self._vbuf[:, :, :P0].copy_(layer._vbuf[:, :, :P0])
+        self._stored = self._pmax = P0
+        self._ktail = torch.empty(1, n_kv_heads, bounded_tail_rows(P0, B, interval), d, dtype=dt, device=dev)
+        self._vtail = torch.empty_like(self._ktail)
+        self._split, self._tail = True, 0
+        self._plen = torch.full((1,), P0, dtype=torch.int32, device=dev)
+        if method != _kvc.STREAMINGLLM:
+            self._qring = torch.empty(1, hq, W, d, dtype=dt, device=dev)
+        self._kout = torch.empty(1, hq, B, d, dtype=dt, device=dev)
+        self._vout = torch.empty_like(self._kout)
+        self._cluster = cluster
+        self._devlen, self._dev_counter, self._dev_hold = True, counter, True
+        counter.zero_()
+        return self
+
+    def enter_device_length(self, *a, **kw):
+        raise NotImplementedError(f"kvcache_factory_amd: {type(self).__name__} is in its own device-length mode from the start")
+
+    def grow_tail(self):
+        raise NotImplementedError("kvcache_factory_amd: the tail of a BoundedDeviceLayer never grows")
+
+    def _fixed(self, *a, **kw):
+        raise NotImplementedError("kvcache_factory_amd: a BoundedDeviceLayer keeps fixed buffers for one sequence and decodes through "
+                                  "the fused step only (no reference-shaped update, no batch reordering)")
+
+    update = _map_batch = _fixed
+
+    def rows(self):
+        """(P, T) of the host mirror."""
+        return self._stored, self._tail
+
+    def _decode_attend_dev(self, query_states, key_states, value_states, scaling):
+        from . import _kvc
+        b, hkv, t, _ = key_states.shape
+        cap = self._ktail.shape[2]
+        if b != 1 or t != 1:
+            raise NotImplementedError(f"kvcache_factory_amd: a BoundedDeviceLayer takes one-token steps of one sequence, got {b} x {t}")
+        if self._tail + t > cap:
+            raise RuntimeError(f"kvcache_factory_amd: the fixed tail holds {self._tail} of {cap} rows: the owner did not call "
+                               "maybe_compress() after the last step")
+        pcap = self._kbuf.shape[2]
+        key = (query_states.stride(), key_states.stride())
+        if self._dev_ws_key != key:
+            nbytes = _kvc.decode_dev_plan(query_states, key_states, self._kbuf, pcap, self._ktail)[1]
+            self._dev_ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self._ktail.device)
+            self._dev_ws_key = key
+        if self._qring is None:
+            out = _kvc.decode_step_dev(query_states, key_states, value_states, self._kbuf, self._vbuf, pcap, self._ktail, self._vtail,
+                                       self._dev_counter, scaling, rows_b=self._plen, ws=self._dev_ws)
+        else:
+            out = _kvc.decode_step_dev_ring(query_states, key_states, value_states, self._kbuf, self._vbuf, pcap, self._ktail,
+                                            self._vtail, self._dev_counter, scaling, self._qring, rows_b=self._plen, ws=self._dev_ws)
+        if not self._dev_hold:
+            self.advance(t)
+        return out
+
+    def maybe_compress(self):
+        """The trigger, from the host mirror, after the owner advanced it for a step.  -> whether the layer compressed."""
+        from . import _kvc
+        from . import pyramidkv_utils as pu
+        method, B, W = self._plan
+        P, T = self._stored, self._tail
+        if not decode_trigger(P, T, B, W, self.interval):
+            return False
+        cl = self._cluster
+        _kvc.decode_compress(method, self._qring, T % W, self._kbuf, self._vbuf, P, self._ktail, self._vtail, T,
+                             (self._kout, self._vout), W, B - W, cl.kernel_size, cl.pooling, pu.TIE_MODE)
+        self._kbuf[:, :, :B].copy_(self._kout)
+        self._vbuf[:, :, :B].copy_(self._vout)
+        self._plen.fill_(B)
+        self._dev_counter.zero_()
+        self._stored = self._pmax = B
+        self._tail = 0
+        self.compressions += 1
+        return True
 
 
 class HeavyHitterLayer(CompressedDynamicLayer):

@@ -607,10 +607,11 @@ __attribute__((visibility("default"))) size_t kvc_decode_dev_workspace_bytes(con
     return kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, kvc::decode_dev_splits(p->bsz, p->n_q_heads, p->new_rows, rows));
 }
 
-__attribute__((visibility("default"))) int kvc_decode_step_dev(const kvc_decode_params* p, int32_t tail_capacity, const int32_t* tail_rows_dev,
-                                                               const int32_t* prefix_rows_b, const void* q, const void* k_new, const void* v_new,
-                                                               const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail, void* out,
-                                                               void* workspace, size_t workspace_bytes, void* hip_stream) {
+namespace {
+// kvc_decode_step_dev's checks, every one before any pointer is used, and the kernels' arguments
+int decode_dev_args(const kvc_decode_params* p, int32_t tail_capacity, const int32_t* tail_rows_dev, const int32_t* prefix_rows_b,
+                    const void* q, const void* k_new, const void* v_new, const void* k_prefix, const void* v_prefix, void* k_tail,
+                    void* v_tail, void* out, void* workspace, size_t workspace_bytes, kvc::DecodeDevArgs& da) {
     if (int rc = decode_dev_check(p, tail_capacity)) return rc;
     if (!tail_rows_dev) return fail(KVC_ERR_INVALID, "tail_rows_dev is NULL");
     if (((uintptr_t)tail_rows_dev) % 4) return fail(KVC_ERR_ALIGNMENT, "tail_rows_dev is not 4-byte aligned");
@@ -624,7 +625,6 @@ __attribute__((visibility("default"))) int kvc_decode_step_dev(const kvc_decode_
                                p->prefix_stride_b, p->prefix_stride_h, p->tail_stride_b, p->tail_stride_h,
                                p->out_stride_b, p->out_stride_h, p->out_stride_l};
     for (int64_t sd : strides) if ((sd * es) % 16) return fail(KVC_ERR_ALIGNMENT, "a stride is not a multiple of 16 bytes");
-    kvc::DecodeDevArgs da;
     std::memset(&da, 0, sizeof(da));
     kvc::DecodeArgs& a = da.a;
     a.q = q; a.k_new = k_new; a.v_new = v_new; a.k_prefix = k_prefix; a.v_prefix = v_prefix; a.k_tail = k_tail; a.v_tail = v_tail; a.out = out;
@@ -643,9 +643,44 @@ __attribute__((visibility("default"))) int kvc_decode_step_dev(const kvc_decode_
         while (s > 1 && kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, s) > workspace_bytes) --s;
         a.splits = s; a.part = static_cast<float*>(workspace);
     }
+    return KVC_OK;
+}
+}  // namespace
+
+__attribute__((visibility("default"))) int kvc_decode_step_dev(const kvc_decode_params* p, int32_t tail_capacity, const int32_t* tail_rows_dev,
+                                                               const int32_t* prefix_rows_b, const void* q, const void* k_new, const void* v_new,
+                                                               const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail, void* out,
+                                                               void* workspace, size_t workspace_bytes, void* hip_stream) {
+    kvc::DecodeDevArgs da;
+    if (int rc = decode_dev_args(p, tail_capacity, tail_rows_dev, prefix_rows_b, q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, out,
+                                 workspace, workspace_bytes, da)) return rc;
     if (int rc = kvc::launch_decode_step_dev(da, p->dtype, p->head_dim, static_cast<hipStream_t>(hip_stream)))
         return fail(rc, "no device-counted decode kernel for dtype %d head_dim %d", p->dtype, p->head_dim);
     return hip_ok("device-counted decode step launch");
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_dev_ring(const kvc_decode_params* p, int32_t tail_capacity, const int32_t* tail_rows_dev,
+                                                                    const int32_t* prefix_rows_b, const void* q, const void* k_new,
+                                                                    const void* v_new, const void* k_prefix, const void* v_prefix, void* k_tail,
+                                                                    void* v_tail, void* out, void* q_ring, int32_t ring_rows,
+                                                                    int64_t ring_stride_b, int64_t ring_stride_h, void* workspace,
+                                                                    size_t workspace_bytes, void* hip_stream) {
+    if (int rc = decode_dev_check(p, tail_capacity)) return rc;
+    if (ring_rows < 1) return fail(KVC_ERR_INVALID, "ring_rows %d must be >= 1", ring_rows);
+    if (!q_ring) return fail(KVC_ERR_INVALID, "q_ring is NULL");
+    const int es = esize_of(p->dtype);
+    if (((uintptr_t)q_ring) % 16 || (ring_stride_b * es) % 16 || (ring_stride_h * es) % 16)
+        return fail(KVC_ERR_INVALID, "q_ring and its strides must be 16-byte aligned");
+    if (ring_stride_h < (int64_t)ring_rows * p->head_dim || ring_stride_b < (int64_t)p->n_q_heads * ring_stride_h)
+        return fail(KVC_ERR_INVALID, "ring strides (%lld, %lld) smaller than its [heads=%d][rows=%d][head_dim=%d] extent",
+                    (long long)ring_stride_b, (long long)ring_stride_h, p->n_q_heads, ring_rows, p->head_dim);
+    kvc::DecodeDevRingArgs ra;
+    if (int rc = decode_dev_args(p, tail_capacity, tail_rows_dev, prefix_rows_b, q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, out,
+                                 workspace, workspace_bytes, ra.d)) return rc;
+    ra.ring = q_ring; ra.ring_stride_b = ring_stride_b; ra.ring_stride_h = ring_stride_h; ra.ring_rows = ring_rows;
+    if (int rc = kvc::launch_decode_step_dev_ring(ra, p->dtype, p->head_dim, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no device-counted decode kernel for dtype %d head_dim %d", p->dtype, p->head_dim);
+    return hip_ok("device-counted decode step (query ring) launch");
 }
 
 // ---- quantized decode cache (kvc_quant.hip) -------------------------------------------------------------------------------

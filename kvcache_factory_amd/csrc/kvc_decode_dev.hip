@@ -61,6 +61,37 @@ __global__ __launch_bounds__(64) void decode_dev_append_kernel(const DecodeDevAr
         reinterpret_cast<uint4*>(dst)[c] = reinterpret_cast<const uint4*>(src)[c];
 }
 
+// decode_dev_append_kernel plus the query ring, in the same launch.  grid = (rows = new_rows, 2 * b * H_kv + b * H_q), block = 64:
+// blocks y < 2 * b * H_kv are the append's (K for the first b * H_kv, V for the rest); block y = 2 * b * H_kv + b' * H_q + h copies
+// query row i of head h to ring slot (T + i) % W.  Only rows i >= new_rows - W are copied, so a slot has one writer per call.
+__global__ __launch_bounds__(64) void decode_dev_append_ring_kernel(const DecodeDevRingArgs ra) {
+    const DecodeDevArgs& da = ra.d;
+    const DecodeArgs& a = da.a;
+    const int i = blockIdx.x, y = blockIdx.y, kv_blocks = a.bsz * a.n_kv_heads;
+    const int pieces = a.row_bytes >> 4;
+    const int T = tail_of(da);
+    const char* src;
+    char* dst;
+    if (y < 2 * kv_blocks) {
+        const int which = y >= kv_blocks, bg = which ? y - kv_blocks : y;
+        const int b = bg / a.n_kv_heads, g = bg % a.n_kv_heads;
+        src = reinterpret_cast<const char*>(which ? a.v_new : a.k_new) +
+            ((int64_t)b * a.new_stride_b + (int64_t)g * a.new_stride_h + (int64_t)i * a.new_stride_l) * a.esize;
+        dst = reinterpret_cast<char*>(which ? a.v_tail : a.k_tail) +
+            ((int64_t)b * a.tail_stride_b + (int64_t)g * a.tail_stride_h) * a.esize + (int64_t)(T + i) * a.row_bytes;
+    } else {
+        if (i < a.new_rows - ra.ring_rows) return;                           // an older row of this step: its slot belongs to a later one
+        const int bh = y - 2 * kv_blocks, b = bh / a.n_q_heads, h = bh % a.n_q_heads;
+        const int slot = (T + i) % ra.ring_rows;                             // T + i >= 0
+        src = reinterpret_cast<const char*>(a.q) +
+            ((int64_t)b * a.q_stride_b + (int64_t)h * a.q_stride_h + (int64_t)i * a.q_stride_l) * a.esize;
+        dst = reinterpret_cast<char*>(ra.ring) +
+            ((int64_t)b * ra.ring_stride_b + (int64_t)h * ra.ring_stride_h) * a.esize + (int64_t)slot * a.row_bytes;
+    }
+    for (int c = threadIdx.x; c < pieces; c += 64)
+        reinterpret_cast<uint4*>(dst)[c] = reinterpret_cast<const uint4*>(src)[c];
+}
+
 // grid = (b * H_q, new_rows, splits of the bound), block = 256 (4 waves); LPR lanes share a row (16 bytes each)
 template <int DT, int D>
 __global__ __launch_bounds__(256) void decode_dev_attention_kernel(const DecodeDevArgs da) {
@@ -185,13 +216,38 @@ int decode_dev_splits(int bsz, int n_q_heads, int new_rows, int rows) {
     return bsz > 1 ? decode_rows_splits(bsz, n_q_heads, new_rows, rows) : decode_splits(bsz, n_q_heads, new_rows, rows);
 }
 
+namespace {
 // a.splits: the splits the workspace handed over can hold (1 without one); the bound fixes rows_per_split and the grid
-int launch_decode_step_dev(DecodeDevArgs da, int dtype, int head_dim, hipStream_t st) {
+void plan_of_bound(DecodeDevArgs& da) {
     DecodeArgs& a = da.a;
     const int rows = a.prefix_rows + da.tail_capacity;                       // the bound: no step sees more
     if (a.splits < 1 || a.part == nullptr) a.splits = 1;
     a.rows_per_split = a.splits == 1 ? rows : ((rows + a.splits - 1) / a.splits + 63) / 64 * 64;
     if (a.splits > 1) a.splits = (rows + a.rows_per_split - 1) / a.rows_per_split;
+}
+}  // namespace
+
+// launch_decode_step_dev with the ring rows written by the append launch: the same number of launches, the same attention and
+// combine kernels with the same arguments
+int launch_decode_step_dev_ring(DecodeDevRingArgs ra, int dtype, int head_dim, hipStream_t st) {
+    plan_of_bound(ra.d);
+    const DecodeDevArgs& da = ra.d;
+    const DecodeArgs& a = da.a;
+    const dim3 grid((unsigned)(a.bsz * a.n_q_heads), (unsigned)a.new_rows, (unsigned)a.splits), cgrid((unsigned)(a.bsz * a.n_q_heads), (unsigned)a.new_rows);
+    const dim3 agrid((unsigned)a.new_rows, (unsigned)(a.bsz * (2 * a.n_kv_heads + a.n_q_heads)));
+#define KVC_CASE(DT_, D_) if (dtype == DT_ && head_dim == D_) { \
+        hipLaunchKernelGGL(decode_dev_append_ring_kernel, agrid, dim3(64), 0, st, ra); \
+        hipLaunchKernelGGL((decode_dev_attention_kernel<DT_, D_>), grid, dim3(256), 0, st, da); \
+        if (a.splits > 1) hipLaunchKernelGGL((decode_dev_combine_kernel<DT_, D_>), cgrid, dim3(D_), 0, st, da); return 0; }
+    KVC_CASE(KVC_BF16, 128) KVC_CASE(KVC_BF16, 64) KVC_CASE(KVC_FP16, 128) KVC_CASE(KVC_FP16, 64)
+    KVC_CASE(KVC_FP32, 128) KVC_CASE(KVC_FP32, 64)
+#undef KVC_CASE
+    return KVC_ERR_UNSUPPORTED;
+}
+
+int launch_decode_step_dev(DecodeDevArgs da, int dtype, int head_dim, hipStream_t st) {
+    plan_of_bound(da);
+    const DecodeArgs& a = da.a;
     const dim3 grid((unsigned)(a.bsz * a.n_q_heads), (unsigned)a.new_rows, (unsigned)a.splits), cgrid((unsigned)(a.bsz * a.n_q_heads), (unsigned)a.new_rows);
 #define KVC_CASE(DT_, D_) if (dtype == DT_ && head_dim == D_) { \
         hipLaunchKernelGGL(decode_dev_append_kernel, dim3((unsigned)a.new_rows, (unsigned)(a.bsz * a.n_kv_heads), 2), dim3(64), 0, st, da); \

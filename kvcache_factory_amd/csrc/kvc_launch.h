@@ -176,6 +176,13 @@ struct DecodeDevArgs {     // kvc_decode_dev.hip: DecodeArgs (pruned_rows = 0, t
     int tail_capacity;                                // rows the tail buffers hold (the clamp of the counter)
 };
 
+struct DecodeDevRingArgs { // kvc_decode_dev.hip: DecodeDevArgs + the query ring the append launch also writes
+    DecodeDevArgs d;
+    void* ring;                                       // [b][Hq][ring_rows][D], rows dense: query row i -> slot (T + i) % ring_rows
+    int64_t ring_stride_b, ring_stride_h;             // elements
+    int ring_rows;
+};
+
 struct QuantArgs {         // kvc_quant.hip: quantize / de-quantize rows [row0, row0 + rows) of one segment (include/kvc.h layout)
     const void* src; void* dst;                       // [b][h][row][D] elements (quantize reads src, de-quantize writes dst)
     uint8_t* codes; const uint8_t* codes_in; float* meta; const float* meta_in;
@@ -287,6 +294,7 @@ int launch_decode_combine(const DecodeArgs& a, int dtype, int head_dim, hipStrea
 int launch_decode_step_rows(DecodeRowsArgs a, int dtype, int head_dim, hipStream_t st);     // kvc_decode_rows.hip
 int decode_rows_splits(int bsz, int n_q_heads, int new_rows, int rows);
 int launch_decode_step_dev(DecodeDevArgs a, int dtype, int head_dim, hipStream_t st);       // kvc_decode_dev.hip
+int launch_decode_step_dev_ring(DecodeDevRingArgs a, int dtype, int head_dim, hipStream_t st);
 int decode_dev_splits(int bsz, int n_q_heads, int new_rows, int rows);
 int launch_quantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_dequantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
