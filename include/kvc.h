@@ -361,6 +361,47 @@ int kvc_decode_step_scored(const kvc_decode_scored_params* p, const void* q, con
                            float* score_prefix, float* score_tail, void* out,
                            void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* kvc_decode_step_dev_scored: kvc_decode_step_scored with the LENGTHS read on the device, so that H2O's scored step can be captured in
+ * a HIP graph and replayed while the cache grows and is evicted.  The contract is kvc_decode_step_dev's word for word plus
+ * kvc_decode_step_scored's score rule.  The tail buffers hold tail_capacity rows per KV head, score_tail tail_capacity scores per
+ * query head;
+ *     T = clamp(*tail_rows_dev, 0, tail_capacity - new_rows)
+ * is read by the kernels only, p->step.tail_rows is ignored.  P_b = prefix_rows_b[b] clamped to [0, p->step.prefix_rows], or
+ * p->step.prefix_rows when the pointer is NULL.  The step's rows are appended at tail row T; token i of batch row b sees prefix rows
+ * [0, P_b) and tail rows [0, T + i + 1); virtual row r is prefix row r for r < P_b, else tail row r - P_b.
+ *   - THE RULE: nothing the host passes depends on T (or on P_b).  The grids, the rows of a split and the row stride of the logits
+ *     come from the bound p->step.prefix_rows + tail_capacity (kvc_decode_step_dev's plan with its full workspace); a workgroup
+ *     whose first row is at or past the visible rows returns before it loads anything and writes nothing, and the merge of the
+ *     splits and the scoring read only the splits that ran.  The library only READS the counter and the prefix lengths.
+ *   - scores: for every new token i in ascending order and every virtual row r visible to it (its own row included)
+ *     score[h][r] += exp2(s - M) / Lsum in fp32, s the row's log2-domain logit from the attention kernel's fmaf chain, (M, Lsum) of
+ *     the (head, token) merged over the splits that ran, in the order of the merge of the splits.  Prefix rows use score_prefix
+ *     [b][H_q][>= prefix_rows], tail rows score_tail [b][H_q][>= tail_capacity], one score per query head.  A row appended by this
+ *     step starts from 0, whatever its slot held.
+ *   - never touched: prefix score slots [P_b, prefix_rows) and tail score slots at or past T + new_rows are neither read nor written;
+ *     the same holds for K, V and the workspace behind the visible rows.  No atomics: every probability is owned by one thread, the
+ *     result does not depend on scheduling.  No counter value makes a kernel read or write outside the buffers.
+ *   - `out` has kvc_decode_step_dev's bytes for the same arguments and its full workspace; when T + new_rows == tail_capacity and
+ *     every P_b == prefix_rows (so that the two split plans coincide), `out` and every score are kvc_decode_step_scored's bit for bit.
+ *   - workspace: kvc_decode_dev_scored_workspace_bytes(p, tail_capacity) bytes, 16-byte aligned, REQUIRED in full (NULL, misaligned
+ *     or short: KVC_ERR_WORKSPACE): the partial results of every split of the bound's plan — (M, Lsum) are stored with one split
+ *     too — and the logits [b * H_q][new_rows][prefix_rows + tail_capacity] fp32, indexed by virtual row.  Its contents before the
+ *     call do not matter.  A captured call must own its workspace (and `out`) for as long as the graph lives.
+ *   - launches: append, attention, merge of the splits (only when the plan has several), scoring — at most one more than
+ *     kvc_decode_step_dev.
+ * Every argument is checked before any pointer is used: everything kvc_decode_step_dev checks, then NULL score pointers
+ * (KVC_ERR_INVALID; score_prefix may be NULL when prefix_rows == 0), score pointers that are not 4-byte aligned (KVC_ERR_ALIGNMENT),
+ * score strides (in floats) smaller than prefix_rows / tail_capacity, and score buffers that overlap each other or `out`
+ * (KVC_ERR_INVALID).  Enqueue-only: no allocation, no synchronisation, no host read, no kernel attribute set on the launch path. */
+size_t kvc_decode_dev_scored_workspace_bytes(const kvc_decode_scored_params* p, int32_t tail_capacity);
+int kvc_decode_step_dev_scored(const kvc_decode_scored_params* p, int32_t tail_capacity,
+                               const int32_t* tail_rows_dev /* device, 1 int32 */,
+                               const int32_t* prefix_rows_b /* device [bsz], nullable: NULL = prefix_rows for every row */,
+                               const void* q, const void* k_new, const void* v_new,
+                               const void* k_prefix, const void* v_prefix, void* k_tail, void* v_tail,
+                               float* score_prefix, float* score_tail, void* out,
+                               void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* kvc_decode_evict: the S = P + T rows of one layer become k + W rows.  With the virtual row numbering of kvc_decode_compress
  * (row r < P: prefix row r of query head h; else tail row r - P of KV head h / G) and score[h][r] read from score_prefix /
  * score_tail alike:

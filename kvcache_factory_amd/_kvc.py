@@ -33,7 +33,7 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_decode_compress_workspace_bytes", "kvc_decode_compress", "kvc_decode_rows_workspace_bytes",
            "kvc_decode_step_rows", "kvc_decode_scored_workspace_bytes", "kvc_decode_step_scored",
            "kvc_decode_evict_workspace_bytes", "kvc_decode_evict", "kvc_decode_dev_workspace_bytes", "kvc_decode_step_dev",
-           "kvc_decode_step_dev_ring")
+           "kvc_decode_step_dev_ring", "kvc_decode_dev_scored_workspace_bytes", "kvc_decode_step_dev_scored")
 
 
 class KvcError(RuntimeError):
@@ -201,6 +201,9 @@ def lib():
         L.kvc_decode_scored_workspace_bytes.argtypes = [ds]
         L.kvc_decode_scored_workspace_bytes.restype = sz
         L.kvc_decode_step_scored.argtypes = [ds] + [vp] * 11 + [sz, vp]
+        L.kvc_decode_dev_scored_workspace_bytes.argtypes = [ds, ctypes.c_int32]
+        L.kvc_decode_dev_scored_workspace_bytes.restype = sz
+        L.kvc_decode_step_dev_scored.argtypes = [ds, ctypes.c_int32] + [vp] * 13 + [sz, vp]
         L.kvc_decode_evict_workspace_bytes.argtypes = [de]
         L.kvc_decode_evict_workspace_bytes.restype = sz
         L.kvc_decode_evict.argtypes = [de] + [vp] * 11 + [sz, vp]
@@ -684,6 +687,89 @@ def decode_step_scored(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail,
     _check(_call(dev, lib().kvc_decode_step_scored, ctypes.byref(sp), _ptr(q), _ptr(k_new), _ptr(v_new),
                  _ptr(k_prefix if prefix_rows else None), _ptr(v_prefix if prefix_rows else None), _ptr(k_tail), _ptr(v_tail),
                  _ptr(score_prefix if prefix_rows else None), _ptr(score_tail), _ptr(out), _ptr(ws), nbytes, _stream(dev)))
+    return out
+
+
+_DEV_SCORED_PLANS = {}                                   # layout key -> (DecodeScoredParams, workspace bytes) of decode_step_dev_scored
+
+
+def decode_dev_scored_plan(q, k_new, k_prefix, prefix_rows, k_tail, score_prefix, score_tail, out_strides=None):
+    """(kvc_decode_scored_params, workspace bytes) of decode_step_dev_scored for this layout, built once per layout and reused as
+    decode_dev_plan's: between calls only pointers change.  out_strides: (b, h, l) strides of a caller-owned `out`, None = a dense
+    [b, t, H_q, D]."""
+    b, hq, t, D = q.shape
+    cap = k_tail.shape[2]
+    if out_strides is None:
+        out_strides = (t * hq * D, D, hq * D)
+    sps = (score_prefix.stride(0), score_prefix.stride(1)) if score_prefix is not None else (0, 0)
+    key = (q.dtype, q.device, b, hq, k_new.shape[1], t, D, prefix_rows, cap, q.stride(), k_new.stride(), k_prefix.stride(0),
+           k_prefix.stride(1), k_tail.stride(0), k_tail.stride(1), sps, score_tail.stride(0), score_tail.stride(1), out_strides)
+    plan = _DEV_SCORED_PLANS.get(key)
+    if plan is None:
+        if len(_DEV_SCORED_PLANS) >= 256:
+            _DEV_SCORED_PLANS.clear()
+        sp = DecodeScoredParams()
+        p = sp.step
+        p.dtype, p.bsz, p.n_q_heads, p.n_kv_heads, p.head_dim = DTYPES[q.dtype], b, hq, k_new.shape[1], D
+        p.prefix_rows, p.tail_rows, p.new_rows = prefix_rows, 0, t
+        p.q_stride_b, p.q_stride_h, p.q_stride_l = q.stride(0), q.stride(1), q.stride(2)
+        p.new_stride_b, p.new_stride_h, p.new_stride_l = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+        p.prefix_stride_b, p.prefix_stride_h = k_prefix.stride(0), k_prefix.stride(1)
+        p.tail_stride_b, p.tail_stride_h = k_tail.stride(0), k_tail.stride(1)
+        p.out_stride_b, p.out_stride_h, p.out_stride_l = out_strides
+        p.scaling = 1.0                                  # checked with the layout; the call writes its own
+        sp.score_prefix_stride_b, sp.score_prefix_stride_h = sps
+        sp.score_tail_stride_b, sp.score_tail_stride_h = score_tail.stride(0), score_tail.stride(1)
+        nbytes = lib().kvc_decode_dev_scored_workspace_bytes(ctypes.byref(sp), cap)
+        err = lib().kvc_last_error().decode()
+        if nbytes == 0 and err:
+            raise KvcError(ERR_INVALID, err)
+        plan = _DEV_SCORED_PLANS[key] = (sp, nbytes)
+    return plan
+
+
+def decode_step_dev_scored(q, k_new, v_new, k_prefix, v_prefix, prefix_rows, k_tail, v_tail, tail_counter, score_prefix, score_tail,
+                           scaling, rows_b=None, ws=None, out=None):
+    """decode_step_scored whose lengths live on the device (kvc_decode_step_dev_scored): the step's rows are appended at tail row
+    T = clamp(tail_counter[0], 0, capacity - t) of k_tail / v_tail [b, H_kv, capacity, D], batch row b sees the first
+    clamp(rows_b[b], 0, prefix_rows) prefix rows (rows_b None: prefix_rows) and token i tail rows [0, T + i + 1); every visible row's
+    fp32 score — score_prefix [b, H_q, >= prefix_rows], score_tail [b, H_q, >= capacity], one per QUERY head — grows by the token's
+    softmax probability, the step's own rows starting from 0.  tail_counter (int32 [1]) and rows_b (int32 [b]) are only read.
+    Nothing passed to the library depends on the lengths, so a captured call replays for every later one.  ws: a caller-owned uint8
+    workspace of at least decode_dev_scored_plan(...)[1] bytes and out: a caller-owned [b, t, H_q, D] buffer — a captured call must
+    own both; without them the call uses the pool and a fresh tensor."""
+    _require_gpu(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, tail_counter, rows_b, score_prefix, score_tail)
+    dev = _one_device(q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, tail_counter, rows_b, score_prefix, score_tail, ws, out)
+    q, k_new, v_new = _last_dim_contig(q), _last_dim_contig(k_new), _last_dim_contig(v_new)
+    if k_new.stride() != v_new.stride():        # K comes out of RoPE contiguous, V is the projection's transposed view
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    b, hq, t, D = q.shape
+    cap = k_tail.shape[2]
+    assert tail_counter.dtype == torch.int32 and tail_counter.numel() == 1
+    assert rows_b is None or (rows_b.dtype == torch.int32 and rows_b.shape == (b,) and rows_b.is_contiguous())
+    assert 0 <= prefix_rows <= k_prefix.shape[2] and v_prefix.shape[2] >= prefix_rows
+    assert k_new.shape == v_new.shape and k_new.shape[2] == t
+    assert k_tail.stride() == v_tail.stride() and k_tail.shape == v_tail.shape and k_prefix.stride() == v_prefix.stride()
+    for x in (k_prefix, v_prefix, k_tail, v_tail):
+        assert x.stride(3) == 1 and x.stride(2) == D, "cache rows must be dense"
+    if prefix_rows:
+        assert score_prefix.dtype == torch.float32 and score_prefix.shape[:2] == (b, hq) and score_prefix.shape[2] >= prefix_rows and \
+            score_prefix.stride(2) == 1
+    assert score_tail.dtype == torch.float32 and score_tail.shape[:2] == (b, hq) and score_tail.shape[2] >= cap and score_tail.stride(2) == 1
+    if out is None:
+        out = torch.empty(b, t, hq, D, dtype=q.dtype, device=dev)
+    else:
+        assert out.shape == (b, t, hq, D) and out.dtype == q.dtype and out.stride(3) == 1
+    sp, nbytes = decode_dev_scored_plan(q, k_new, k_prefix, prefix_rows, k_tail, score_prefix if prefix_rows else None, score_tail,
+                                        (out.stride(0), out.stride(2), out.stride(1)))
+    sp.step.scaling = scaling
+    if ws is None:
+        ws = workspace(dev, nbytes)
+    else:
+        assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    _check(_call(dev, lib().kvc_decode_step_dev_scored, ctypes.byref(sp), cap, _ptr(tail_counter), _ptr(rows_b), _ptr(q), _ptr(k_new),
+                 _ptr(v_new), _ptr(k_prefix if prefix_rows else None), _ptr(v_prefix if prefix_rows else None), _ptr(k_tail), _ptr(v_tail),
+                 _ptr(score_prefix if prefix_rows else None), _ptr(score_tail), _ptr(out), _ptr(ws), ws.numel(), _stream(dev)))
     return out
 
 

@@ -585,7 +585,41 @@ def bounded_tail_rows(P0, B, interval):
     return max(interval, B + interval - P0)
 
 
-class BoundedDeviceLayer(CompressedDynamicLayer):
+class _FixedBuffersLayer(CompressedDynamicLayer):
+    """What the two bounded layers of graph-replayed decoding share: they are made from a prefilled layer (`adopt`), keep every
+    buffer for the whole generation and decode through the fused step only, one sequence, one token a step."""
+
+    def prefill(self, *a, **kw):
+        raise NotImplementedError(f"kvcache_factory_amd: a {type(self).__name__} is made from a prefilled layer "
+                                  f"({type(self).__name__}.adopt)")
+
+    def enter_device_length(self, *a, **kw):
+        raise NotImplementedError(f"kvcache_factory_amd: {type(self).__name__} is in its own device-length mode from the start")
+
+    def grow_tail(self):
+        raise NotImplementedError(f"kvcache_factory_amd: the tail of a {type(self).__name__} never grows")
+
+    def _fixed(self, *a, **kw):
+        raise NotImplementedError(f"kvcache_factory_amd: a {type(self).__name__} keeps fixed buffers for one sequence and decodes "
+                                  "through the fused step only (no reference-shaped update, no batch reordering)")
+
+    update = _map_batch = _fixed
+
+    def rows(self):
+        """(P, T) of the host mirror."""
+        return self._stored, self._tail
+
+    def _one_token(self, key_states):
+        b, _, t, _ = key_states.shape
+        cap = self._ktail.shape[2]
+        if b != 1 or t != 1:
+            raise NotImplementedError(f"kvcache_factory_amd: a {type(self).__name__} takes one-token steps of one sequence, got {b} x {t}")
+        if self._tail + t > cap:
+            raise RuntimeError(f"kvcache_factory_amd: the fixed tail holds {self._tail} of {cap} rows: the owner did not call "
+                               f"{self._after_step}() after the last step")
+
+
+class BoundedDeviceLayer(_FixedBuffersLayer):
     """Decode-stage compression in DEVICE-LENGTH MODE (graph_decode.GraphDecoder(model, interval=N)): DecodeCompressedLayer's budget
     and trigger (decode_budget, decode_trigger) on a layer whose every address is fixed for the whole generation, so that ONE captured
     step replays however long it runs.  One sequence (bsz = 1), one-token steps.
@@ -619,8 +653,7 @@ class BoundedDeviceLayer(CompressedDynamicLayer):
         super().reset()
         self._clear_bounded()
 
-    def prefill(self, *a, **kw):
-        raise NotImplementedError("kvcache_factory_amd: a BoundedDeviceLayer is made from a prefilled layer (BoundedDeviceLayer.adopt)")
+    _after_step = "maybe_compress"
 
     @classmethod
     def adopt(cls, layer, cluster, interval, counter, n_kv_heads):
@@ -660,31 +693,10 @@ class BoundedDeviceLayer(CompressedDynamicLayer):
         counter.zero_()
         return self
 
-    def enter_device_length(self, *a, **kw):
-        raise NotImplementedError(f"kvcache_factory_amd: {type(self).__name__} is in its own device-length mode from the start")
-
-    def grow_tail(self):
-        raise NotImplementedError("kvcache_factory_amd: the tail of a BoundedDeviceLayer never grows")
-
-    def _fixed(self, *a, **kw):
-        raise NotImplementedError("kvcache_factory_amd: a BoundedDeviceLayer keeps fixed buffers for one sequence and decodes through "
-                                  "the fused step only (no reference-shaped update, no batch reordering)")
-
-    update = _map_batch = _fixed
-
-    def rows(self):
-        """(P, T) of the host mirror."""
-        return self._stored, self._tail
-
     def _decode_attend_dev(self, query_states, key_states, value_states, scaling):
         from . import _kvc
-        b, hkv, t, _ = key_states.shape
-        cap = self._ktail.shape[2]
-        if b != 1 or t != 1:
-            raise NotImplementedError(f"kvcache_factory_amd: a BoundedDeviceLayer takes one-token steps of one sequence, got {b} x {t}")
-        if self._tail + t > cap:
-            raise RuntimeError(f"kvcache_factory_amd: the fixed tail holds {self._tail} of {cap} rows: the owner did not call "
-                               "maybe_compress() after the last step")
+        self._one_token(key_states)
+        t = key_states.shape[2]
         pcap = self._kbuf.shape[2]
         key = (query_states.stride(), key_states.stride())
         if self._dev_ws_key != key:
@@ -720,6 +732,19 @@ class BoundedDeviceLayer(CompressedDynamicLayer):
         self._tail = 0
         self.compressions += 1
         return True
+
+
+def heavy_hitter_budget(cluster, interval):
+    """(B, W) of a layer evicted by H2O's rule for `cluster` (the patched forward's kv_cluster): the one statement of the budget rule,
+    shared by HeavyHitterLayer and BoundedHeavyHitterLayer."""
+    from . import _kvc
+    if getattr(cluster, "_method", None) != _kvc.H2O or getattr(cluster, "merge", None) is not None:
+        raise NotImplementedError(f"kvcache_factory_amd: HeavyHitterCache is H2O's decode-time rule; it has none for "
+                                  f"{type(cluster).__name__} (merge={getattr(cluster, 'merge', None)!r})")
+    W = cluster.window_size
+    if interval < W:
+        raise ValueError(f"HeavyHitterCache: interval {interval} must be >= window_size {W}")
+    return cluster.max_capacity_prompt, W
 
 
 class HeavyHitterLayer(CompressedDynamicLayer):
@@ -804,14 +829,7 @@ class HeavyHitterLayer(CompressedDynamicLayer):
 
     def budget(self, cluster):
         """(B, W) of this layer for `cluster` (the patched forward's kv_cluster)."""
-        from . import _kvc
-        if getattr(cluster, "_method", None) != _kvc.H2O or getattr(cluster, "merge", None) is not None:
-            raise NotImplementedError(f"kvcache_factory_amd: HeavyHitterCache is H2O's decode-time rule; it has none for "
-                                      f"{type(cluster).__name__} (merge={getattr(cluster, 'merge', None)!r})")
-        W = cluster.window_size
-        if self.interval < W:
-            raise ValueError(f"HeavyHitterCache: interval {self.interval} must be >= window_size {W}")
-        return cluster.max_capacity_prompt, W
+        return heavy_hitter_budget(cluster, self.interval)
 
     def decode_attend(self, query_states, key_states, value_states, scaling):
         """One decode step in the SPLIT form (kvc_decode_step_scored): the step's rows [1, H_kv, t, D] go to the tail, every
@@ -903,6 +921,132 @@ class HeavyHitterCache(Cache):
         text = config.get_text_config() if hasattr(config, "get_text_config") else config
         self.interval = interval
         super().__init__(layers=[HeavyHitterLayer(interval) for _ in range(text.num_hidden_layers)])
+
+
+class BoundedHeavyHitterLayer(_FixedBuffersLayer):
+    """H2O's eviction in DEVICE-LENGTH MODE (graph_decode.GraphDecoder(model, heavy_hitter=N)): HeavyHitterLayer's scores, budget and
+    trigger (heavy_hitter_budget, decode_trigger) on a layer whose every address is fixed for the whole generation, so that ONE
+    captured step replays however long it runs.  BoundedDeviceLayer's twin: one sequence (bsz = 1), one-token steps.
+
+    The K / V prefix buffers and the fp32 score prefix buffer hold Pcap = max(P0, B) rows per query head (the prefill's P0 rows and
+    their scores — the prompt's column sums, or zeros for a pass-through prompt — are copied in); how many are in use is a device int32
+    (`_plen`) the step reads as its per-row prefix length.  The tail holds bounded_tail_rows(P0, B, interval) rows — K / V per KV head,
+    scores [1, H_q, cap] per query head — and its length lives in this layer's own device counter.  The step is
+    kvc_decode_step_dev_scored; its workspace and the B-row output buffers of an eviction (K, V, scores) are allocated on entry.
+
+    `_stored` / `_tail` / `true_length` are the host MIRROR, advanced by the owner (`advance`), who then calls `maybe_evict`: when the
+    mirror says so, kvc_decode_evict runs eagerly on the step's stream over (P, T) under pyramidkv_utils.TIE_MODE into the output
+    buffers, device copies move the B rows of K, V and scores back into the fixed prefix buffers, and the prefix-length word (B) and
+    the counter (0) are set by device ops.  Nothing is read from the device.  `after_decode` does nothing here."""
+
+    _after_step = "maybe_evict"
+
+    def __init__(self, interval=128):
+        _check_interval(interval)
+        super().__init__()
+        self.interval = interval
+        self._clear_bounded()
+
+    def _clear_bounded(self):
+        self._plen = None                   # int32 [1] on the device: prefix rows in use (the step's prefix_rows_b)
+        self._sbuf = self._stail = None     # fp32 [1, H_q, Pcap] / [1, H_q, cap]: the scores of the prefix and the tail rows
+        self._kout = self._vout = self._sout = None     # [1, H_q, B(, D)]: where an eviction writes before the rows are copied back
+        self._plan = None                   # (B, W)
+        self.evictions = 0
+
+    def reset(self):
+        super().reset()
+        self._clear_bounded()
+
+    @classmethod
+    def adopt(cls, layer, cluster, interval, counter, n_kv_heads):
+        """The bounded layer that takes over from `layer`, a HeavyHitterLayer right after its prefill (its P0 rows and their scores
+        are copied).  counter: int32 [1] on the layer's device, this layer's own; it is set to 0 here by a device op."""
+        if type(layer) is not HeavyHitterLayer or layer._kbuf is None:
+            raise NotImplementedError(f"kvcache_factory_amd: BoundedHeavyHitterLayer adopts a prefilled HeavyHitterLayer, not a "
+                                      f"{type(layer).__name__}")
+        if layer._split or layer._stored != layer._pmax or layer.evictions:
+            raise NotImplementedError("kvcache_factory_amd: this layer already holds decoded rows; enter the bounded mode right after "
+                                      "the prefill")
+        b, hq, _, d = layer._kbuf.shape
+        if b != 1:
+            raise NotImplementedError(f"kvcache_factory_amd: H2O's decode-time eviction holds one sequence (bsz = 1), got a batch of {b}")
+        self = cls(interval)
+        B, W = self._plan = heavy_hitter_budget(cluster, interval)
+        assert counter.dtype == torch.int32 and counter.numel() == 1 and counter.device == layer._kbuf.device
+        from . import _kvc
+        P0, dt, dev = layer._stored, layer._kbuf.dtype, layer._kbuf.device
+        pcap, cap = max(P0, B), bounded_tail_rows(P0, B, interval)
+        self.dtype, self.device, self.is_initialized = layer.dtype, layer.device, True
+        self.true_length = layer.true_length
+        self._kbuf = torch.empty(1, hq, pcap, d, dtype=dt, device=dev)
+        self._vbuf = torch.empty_like(self._kbuf)
+        self._sbuf = torch.empty(1, hq, pcap, dtype=torch.float32, device=dev)
+        self._kbuf[:, :, :P0].copy_(layer._kbuf[:, :, :P0])
+        self._vbuf[:, :, :P0].copy_(layer._vbuf[:, :, :P0])
+        self._sbuf[:, :, :P0].copy_(layer._sbuf[:, :, :P0])
+        self._stored = self._pmax = P0
+        self._ktail = torch.empty(1, n_kv_heads, cap, d, dtype=dt, device=dev)
+        self._vtail = torch.empty_like(self._ktail)
+        self._stail = torch.empty(1, hq, cap, dtype=torch.float32, device=dev)
+        self._split, self._tail = True, 0
+        self._plen = torch.full((1,), P0, dtype=torch.int32, device=dev)
+        self._kout = torch.empty(1, hq, B, d, dtype=dt, device=dev)
+        self._vout = torch.empty_like(self._kout)
+        self._sout = torch.empty(1, hq, B, dtype=torch.float32, device=dev)
+        # the step's own workspace: its size follows the bound alone (the strides of a step's q / k_new do not enter it)
+        q1, k1 = (torch.empty(1, h, 1, d, dtype=dt, device="meta") for h in (hq, n_kv_heads))
+        nbytes = _kvc.decode_dev_scored_plan(q1, k1, self._kbuf, pcap, self._ktail, self._sbuf, self._stail)[1]
+        self._dev_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._devlen, self._dev_counter, self._dev_hold = True, counter, True
+        counter.zero_()
+        return self
+
+    def scores(self):
+        """fp32 [1, H_q, P + T]: the score of every stored row of the mirror, prefix then tail (a copy; tests and tools)."""
+        P, T = self.rows()
+        if self._sbuf is None:
+            return None
+        return torch.cat([self._sbuf[:, :, :P], self._stail[:, :, :T]], dim=2)
+
+    def scores_state(self):
+        """Copies of the two score buffers (device ops): what `set_scores_state` puts back.  For an owner whose warm-up steps before a
+        capture must leave no trace — a step rewrites its own K / V row, but what it added to the scores stays."""
+        return self._sbuf.clone(), self._stail.clone()
+
+    def set_scores_state(self, state):
+        self._sbuf.copy_(state[0])
+        self._stail.copy_(state[1])
+
+    def _decode_attend_dev(self, query_states, key_states, value_states, scaling):
+        from . import _kvc
+        self._one_token(key_states)
+        out = _kvc.decode_step_dev_scored(query_states, key_states, value_states, self._kbuf, self._vbuf, self._kbuf.shape[2], self._ktail,
+                                          self._vtail, self._dev_counter, self._sbuf, self._stail, scaling, rows_b=self._plen,
+                                          ws=self._dev_ws)
+        if not self._dev_hold:
+            self.advance(key_states.shape[2])
+        return out
+
+    def maybe_evict(self):
+        """The trigger, from the host mirror, after the owner advanced it for a step.  -> whether the layer evicted."""
+        from . import _kvc
+        from . import pyramidkv_utils as pu
+        B, W = self._plan
+        P, T = self._stored, self._tail
+        if not decode_trigger(P, T, B, W, self.interval):
+            return False
+        _kvc.decode_evict(self._kbuf, self._vbuf, P, self._ktail, self._vtail, T, self._sbuf, self._stail, (self._kout, self._vout),
+                          self._sout, W, B - W, pu.TIE_MODE)
+        self._kbuf[:, :, :B].copy_(self._kout)
+        self._vbuf[:, :, :B].copy_(self._vout)
+        self._sbuf[:, :, :B].copy_(self._sout)
+        self._plen.fill_(B)
+        self._dev_counter.zero_()
+        self._stored = self._pmax = B
+        self._tail = 0
+        self.evictions += 1
+        return True
 
 
 def _check_quant_args(nbits, q_group_size, residual_length):

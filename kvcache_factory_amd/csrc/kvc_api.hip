@@ -1828,3 +1828,88 @@ __attribute__((visibility("default"))) int kvc_decode_evict(const kvc_decode_evi
 }
 
 }  // extern "C"
+
+// ---- the scored decode step with the lengths on the device (kvc_decode_dev_scored.hip) -------------------------------------------
+namespace {
+
+// Every field of the params and the capacity, before any pointer is looked at: kvc_decode_step_dev's, then the score strides.
+int dev_scored_check(const kvc_decode_scored_params* sp, int32_t tail_capacity) {
+    if (!sp) return fail(KVC_ERR_INVALID, "params is NULL");
+    const kvc_decode_params* p = &sp->step;
+    if (int rc = decode_dev_check(p, tail_capacity)) return rc;
+    if (p->prefix_rows > 0)
+        if (int rc = score_strides("score_prefix", sp->score_prefix_stride_b, sp->score_prefix_stride_h, p->prefix_rows, p->n_q_heads)) return rc;
+    return score_strides("score_tail", sp->score_tail_stride_b, sp->score_tail_stride_h, tail_capacity, p->n_q_heads);
+}
+
+// (M, Lsum, acc[D]) of every split of the bound's plan — written with one split too — then the logits, one row of the bound's
+// length per (batch row, head, token)
+struct DevScoredLayout { int splits; size_t part, logit, total; };
+DevScoredLayout dev_scored_layout(const kvc_decode_params* p, int32_t tail_capacity) {
+    DevScoredLayout l;
+    const int rows = p->prefix_rows + tail_capacity;
+    const size_t items = (size_t)p->bsz * p->n_q_heads * p->new_rows;
+    l.splits = kvc::decode_dev_splits(p->bsz, p->n_q_heads, p->new_rows, rows);              // kvc_decode_step_dev's plan; the launcher
+    int ran = l.splits;                                                                      // rounds it to whole 64-row blocks alike
+    if (ran > 1) { const int rps = ((rows + ran - 1) / ran + 63) / 64 * 64; ran = (rows + rps - 1) / rps; }
+    l.part = 0;
+    l.logit = align_up(items * (size_t)ran * (p->head_dim + 2) * sizeof(float), 16);
+    l.total = align_up(l.logit + items * (size_t)rows * sizeof(float), 16);
+    return l;
+}
+
+}  // namespace
+
+extern "C" {
+
+__attribute__((visibility("default"))) size_t kvc_decode_dev_scored_workspace_bytes(const kvc_decode_scored_params* p, int32_t tail_capacity) {
+    if (dev_scored_check(p, tail_capacity) != KVC_OK) return 0;
+    g_err[0] = 0;
+    return dev_scored_layout(&p->step, tail_capacity).total;
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_dev_scored(const kvc_decode_scored_params* sp, int32_t tail_capacity,
+                                                                      const int32_t* tail_rows_dev, const int32_t* prefix_rows_b,
+                                                                      const void* q, const void* k_new, const void* v_new,
+                                                                      const void* k_prefix, const void* v_prefix, void* k_tail,
+                                                                      void* v_tail, float* score_prefix, float* score_tail, void* out,
+                                                                      void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (int rc = dev_scored_check(sp, tail_capacity)) return rc;
+    const kvc_decode_params* p = &sp->step;
+    kvc::DecodeDevScoredArgs sa;
+    std::memset(&sa, 0, sizeof(sa));
+    if (int rc = decode_dev_args(p, tail_capacity, tail_rows_dev, prefix_rows_b, q, k_new, v_new, k_prefix, v_prefix, k_tail, v_tail, out,
+                                 nullptr, 0, sa.d)) return rc;
+    if (!score_tail || (p->prefix_rows > 0 && !score_prefix))
+        return fail(KVC_ERR_INVALID, "score_tail (and score_prefix when the prefix has rows) must be non-NULL");
+    if (((uintptr_t)score_tail) % 4 || (p->prefix_rows > 0 && ((uintptr_t)score_prefix) % 4))
+        return fail(KVC_ERR_ALIGNMENT, "score_prefix / score_tail not 4-byte aligned");
+    {   // every score slot has one owner, and `out` is written while the scores are still being read
+        const int es = esize_of(p->dtype);
+        const uintptr_t olo = (uintptr_t)out;
+        const Span so = {olo, olo + (uintptr_t)(((int64_t)(p->bsz - 1) * p->out_stride_b + (int64_t)(p->n_q_heads - 1) * p->out_stride_h +
+                                                 (int64_t)(p->new_rows - 1) * p->out_stride_l + p->head_dim) * es)};
+        const Span stl = score_span(score_tail, sp->score_tail_stride_b, sp->score_tail_stride_h, p->bsz, p->n_q_heads, tail_capacity);
+        bool bad = overlaps(stl, so);
+        if (p->prefix_rows > 0) {
+            const Span spr = score_span(score_prefix, sp->score_prefix_stride_b, sp->score_prefix_stride_h, p->bsz, p->n_q_heads, p->prefix_rows);
+            bad = bad || overlaps(spr, so) || overlaps(spr, stl);
+        }
+        if (bad) return fail(KVC_ERR_INVALID, "score_prefix / score_tail / out overlap each other");
+    }
+    const DevScoredLayout l = dev_scored_layout(p, tail_capacity);
+    if (!workspace) return fail(KVC_ERR_WORKSPACE, "workspace is NULL, need %zu bytes", l.total);
+    if (((uintptr_t)workspace) % 16) return fail(KVC_ERR_WORKSPACE, "workspace must be 16-byte aligned");
+    if (workspace_bytes < l.total) return fail(KVC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, l.total);
+    sa.d.a.splits = l.splits;
+    sa.d.a.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + l.part);
+    sa.logit = reinterpret_cast<float*>(static_cast<char*>(workspace) + l.logit);
+    sa.score_prefix = score_prefix; sa.score_tail = score_tail;
+    sa.sp_sb = sp->score_prefix_stride_b; sa.sp_sh = sp->score_prefix_stride_h;
+    sa.st_sb = sp->score_tail_stride_b; sa.st_sh = sp->score_tail_stride_h;
+    if (int rc = kvc::launch_decode_step_dev_scored(sa, p->dtype, p->head_dim, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no device-counted scored decode kernel for dtype %d head_dim %d", p->dtype, p->head_dim);
+    return hip_ok("device-counted scored decode step launch");
+}
+
+}  // extern "C"

@@ -243,6 +243,14 @@ struct DecodeScoredArgs {  // kvc_decode_scored.hip: DecodeArgs (pruned_rows = 0
     int rows;              // prefix_rows + tail_rows + new_rows (launcher-set)
 };
 
+struct DecodeDevScoredArgs {   // kvc_decode_dev_scored.hip: DecodeDevArgs (d.a.part written with one split too) + the scores
+    DecodeDevArgs d;
+    float* logit;          // [bsz*Hq][new_rows][rows] fp32 workspace: the log2-domain logit of every visible row, by virtual row
+    float* score_prefix; float* score_tail;            // [b][Hq][capacity] fp32, running sums of attention per stored row
+    int64_t sp_sb, sp_sh, st_sb, st_sh;                // floats
+    int rows;              // the bound prefix_rows + tail_capacity: the row stride of `logit` (launcher-set)
+};
+
 struct EvictArgs {         // kvc_decode_evict: candidate scores -> one row per head; gather of K, V and scores from two segments
     const float* score_p; const float* score_t; float* cand;     // cand [bsz*Hq][n] fp32 workspace
     float* score_out;      // [b][Hq][k + window] fp32
@@ -304,6 +312,7 @@ int launch_dequantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype,
 int launch_decode_step_quant_outliers(DecodeQArgs a, const DecodeOArgs& o, int dtype, int head_dim, int nbits, const DecodeArgs& append,
                                       hipStream_t st);
 int launch_decode_step_scored(DecodeScoredArgs a, int dtype, int head_dim, hipStream_t st);   // kvc_decode_scored.hip
+int launch_decode_step_dev_scored(DecodeDevScoredArgs a, int dtype, int head_dim, hipStream_t st);   // kvc_decode_dev_scored.hip
 int launch_evict_scores(const EvictArgs& a, int bsz, hipStream_t st);
 int launch_evict_gather(const EvictArgs& a, int bsz, hipStream_t st);
 int launch_dc_scan(const DcScanArgs& a, int dtype, int head_dim, int bsz, hipStream_t st);

@@ -23,12 +23,19 @@ bounds every layer while it replays: DecodeCompressedCache's budget and trigger 
 addresses for the whole generation.  The tails never grow, so ONE capture serves however many tokens follow; every layer has its
 own device counter (one int32 vector, advanced by one in-graph add), and after a step the host mirrors decide, layer by layer,
 whether a compression runs — eagerly, between two replays, on the same stream.  `tail_rows` is not used in this mode.
+
+    monkeypatch.replace_llama("h2o")
+    dec = GraphDecoder(model, heavy_hitter=128)      # h2o only; one sequence
+
+is the same for H2O's own decode-time rule (HeavyHitterCache's): the prompt goes through an internal HeavyHitterCache, every layer is
+then a cache.BoundedHeavyHitterLayer whose captured step (kvc_decode_step_dev_scored) accumulates the scores, and every `heavy_hitter`
+tokens the mirrors have each layer evict its lowest-scoring rows between two replays.  One capture, no growth, no host read.
 """
 import torch
 
 from . import pyramidkv_utils as pu
-from .cache import (DECODE_METHODS, BoundedDeviceLayer, CompressedDynamicLayer, DecodeCompressedCache, HeavyHitterCache,
-                    QuantizedCompressedCache, _check_interval, decode_budget)
+from .cache import (DECODE_METHODS, BoundedDeviceLayer, BoundedHeavyHitterLayer, CompressedDynamicLayer, DecodeCompressedCache,
+                    HeavyHitterCache, HeavyHitterLayer, QuantizedCompressedCache, _check_interval, decode_budget, heavy_hitter_budget)
 
 _OWN_LAYOUT = ("adakv", "headkv", "think")
 
@@ -48,12 +55,18 @@ def tails_needed(capacity, tail, t):
 class GraphDecoder:
     WARMUP = 2                          # eager steps of the same code before a capture (lazy initialisations, workspaces, plans)
 
-    def __init__(self, model, tail_rows=256, capture=True, interval=None):
+    def __init__(self, model, tail_rows=256, capture=True, interval=None, heavy_hitter=None):
         if isinstance(tail_rows, bool) or not isinstance(tail_rows, int) or tail_rows < 1:
             raise ValueError(f"tail_rows must be an int >= 1, got {tail_rows!r}")
         if interval is not None:
             _check_interval(interval)
-        self.model, self.tail_rows, self.capture, self.interval = model, tail_rows, bool(capture), interval
+        if heavy_hitter is not None:
+            if isinstance(heavy_hitter, bool) or not isinstance(heavy_hitter, int) or heavy_hitter < 1:
+                raise ValueError(f"heavy_hitter must be an int >= 1, got {heavy_hitter!r}")
+            if interval is not None:
+                raise ValueError("kvcache_factory_amd: GraphDecoder takes interval= (snapkv / pyramidkv / streamingllm) or "
+                                 "heavy_hitter= (h2o), not both")
+        self.model, self.tail_rows, self.capture, self.interval, self.heavy_hitter = model, tail_rows, bool(capture), interval, heavy_hitter
         self.config = model.config.get_text_config() if hasattr(model.config, "get_text_config") else model.config
         self._refuse_model()
         self._clusters()
@@ -90,11 +103,21 @@ class GraphDecoder:
         self.method = method
 
     def _clusters(self):
-        """interval mode: every layer's kv_cluster as the patched forward builds it from the config now, through the budget rule —
-        a method without a decode-time rule and merge="pivot" are NotImplementedError, interval < window_size a ValueError."""
+        """interval / heavy_hitter mode: every layer's kv_cluster as the patched forward builds it from the config now, through the
+        mode's budget rule — a method without the rule and merge="pivot" are NotImplementedError, a period < window_size a ValueError."""
+        from .attention import _INIT
+        if self.heavy_hitter is not None:
+            if self.method != "h2o":
+                raise NotImplementedError(f"kvcache_factory_amd: GraphDecoder(heavy_hitter=...) evicts by H2O's accumulated attention; "
+                                          f"{self.method} has no such rule here — it is built for the h2o path only")
+            clusters = []
+            for block in self.model.model.layers:
+                _INIT[self.method](block.self_attn)
+                clusters.append(block.self_attn.kv_cluster)
+                heavy_hitter_budget(clusters[-1], self.heavy_hitter)
+            return clusters
         if self.interval is None:
             return None
-        from .attention import _INIT
         if self.method not in DECODE_METHODS:
             raise NotImplementedError(f"kvcache_factory_amd: {self.method} has no decode-time compression rule here; "
                                       "GraphDecoder(interval=...) is built for the snapkv / pyramidkv / streamingllm paths only")
@@ -138,14 +161,20 @@ class GraphDecoder:
         from .attention import _pending_for
         self._refuse_call(input_ids, past_key_values)
         clusters = self._clusters()
+        heavy = self.heavy_hitter is not None
         if clusters is not None:
+            mode = "heavy_hitter" if heavy else "interval"
             if past_key_values is not None:
-                raise ValueError("kvcache_factory_amd: GraphDecoder(interval=...) builds its own bounded cache; past_key_values must "
+                raise ValueError(f"kvcache_factory_amd: GraphDecoder({mode}=...) builds its own bounded cache; past_key_values must "
                                  f"be None, got a {type(past_key_values).__name__}")
             if input_ids.shape[0] != 1:
-                raise NotImplementedError("kvcache_factory_amd: decode-stage compression has no per-row form; "
-                                          f"GraphDecoder(interval=...) decodes one sequence, got a batch of {input_ids.shape[0]}")
-        cache = DynamicCache(config=self.model.config) if past_key_values is None else past_key_values
+                what = "H2O's decode-time eviction" if heavy else "decode-stage compression"
+                raise NotImplementedError(f"kvcache_factory_amd: {what} has no per-row form; "
+                                          f"GraphDecoder({mode}=...) decodes one sequence, got a batch of {input_ids.shape[0]}")
+        if heavy:                                                            # the patched forward's prefill_heavy_hitter path, unchanged
+            cache = HeavyHitterCache(self.model.config, self.heavy_hitter)
+        else:
+            cache = DynamicCache(config=self.model.config) if past_key_values is None else past_key_values
         if cache.get_seq_length() != 0:
             raise RuntimeError("kvcache_factory_amd: GraphDecoder.prefill starts from an empty cache")
         self._graph = self._cache = None
@@ -162,8 +191,9 @@ class GraphDecoder:
                          use_cache=True, logits_to_keep=1)
         _pending_for(cache).settle()
         layers = tuple(cache.layers)
+        kind = HeavyHitterLayer if heavy else CompressedDynamicLayer
         for layer in layers:
-            if type(layer) is not CompressedDynamicLayer or not layer.can_split():
+            if type(layer) is not kind or not layer.can_split():
                 raise NotImplementedError(f"kvcache_factory_amd: GraphDecoder found a {type(layer).__name__} in the cache after the "
                                           "prefill; graph-replayed decoding covers the plain compressed cache only")
         if clusters is None:
@@ -173,7 +203,8 @@ class GraphDecoder:
                 layer.hold_mirror(True)
         else:                                                                # one counter per layer, one vector for the in-graph add
             self._counter = torch.zeros(len(layers), dtype=torch.int32, device=dev)
-            layers = tuple(BoundedDeviceLayer.adopt(layer, cl, self.interval, self._counter[i:i + 1], self.config.num_key_value_heads)
+            twin, period = (BoundedHeavyHitterLayer, self.heavy_hitter) if heavy else (BoundedDeviceLayer, self.interval)
+            layers = tuple(twin.adopt(layer, cl, period, self._counter[i:i + 1], self.config.num_key_value_heads)
                            for i, (layer, cl) in enumerate(zip(layers, clusters)))
             cache.layers[:] = layers
         self._cache, self._layers = cache, layers
@@ -194,14 +225,18 @@ class GraphDecoder:
 
     def _capture(self):
         """WARMUP eager steps whose effect is taken back (the row they append at T is the row the real step overwrites; counter and
-        positions are set back on the device), then ONE capture of the same body on one stream."""
+        positions are set back on the device, and so are the scores of a heavy-hitter layer), then ONE capture of the same body on one
+        stream."""
         side = torch.cuda.Stream(self._tok.device)
         side.wait_stream(torch.cuda.current_stream(self._tok.device))
         with torch.cuda.stream(side):
+            kept = [layer.scores_state() for layer in self._layers] if self.heavy_hitter is not None else ()
             for _ in range(self.WARMUP):
                 self._body()
                 self._counter.sub_(1)
                 self._pos.sub_(1)
+            for layer, state in zip(self._layers, kept):                     # (heavy_hitter: a warm-up step also added to the scores)
+                layer.set_scores_state(state)
         torch.cuda.current_stream(self._tok.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
@@ -221,7 +256,7 @@ class GraphDecoder:
         """tokens [bsz, 1] (device) -> the static logits buffer [bsz, 1, vocab].  No host read; a graph replay when capture=True."""
         if self._cache is None:
             raise RuntimeError("kvcache_factory_amd: GraphDecoder.step before prefill")
-        if self.interval is None:
+        if self.interval is None and self.heavy_hitter is None:
             for _ in range(tails_needed(self._capacity, self._tail, 1)):
                 self._grow()
         self._tok.copy_(tokens.reshape(self._tok.shape))
@@ -237,6 +272,9 @@ class GraphDecoder:
         if self.interval is not None:
             for layer in self._layers:                                       # host arithmetic; a compression is enqueued eagerly
                 layer.maybe_compress()
+        elif self.heavy_hitter is not None:
+            for layer in self._layers:                                       # host arithmetic; an eviction is enqueued eagerly
+                layer.maybe_evict()
         return self._logits
 
     @torch.no_grad()
