@@ -500,6 +500,39 @@ int kvc_decode_step_quant(const kvc_decode_quant_params* p, const kvc_quant_seg*
                           const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
                           void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
 
+/* kvc_decode_step_quant_dev: kvc_decode_step_quant with BOTH GROWING LENGTHS read on the device, in the spirit of kvc_decode_step_dev,
+ * so that the quantized step can be captured in a HIP graph and replayed while rows are decoded and moved onto the quantized tail.
+ *   prefix    prefix->rows stays a host constant (the prompt is quantized once);
+ *   qtail     the buffers hold qtail->capacity rows (a multiple of group_size), qtail->rows is ignored:
+ *                 Tq = clamp(*qtail_rows_dev, 0, qtail->capacity)
+ *   residual  the buffers hold p->res_capacity rows, p->res_rows is ignored:
+ *                 Rr = clamp(*res_rows_dev, 0, p->res_capacity - new_rows)
+ * Both words are read by the kernels only.  The step's rows are appended at residual row Rr; token i sees prefix rows [0, P), quantized
+ * tail rows [0, Tq) and residual rows [0, Rr + i + 1), in this virtual row order.
+ *   - THE RULE: nothing the host passes depends on Tq or Rr.  The grid and the rows of a split (a multiple of 64) come from the bound
+ *     P + qtail->capacity + res_capacity — the plan kvc_decode_step_quant makes for that many rows; a workgroup whose first virtual
+ *     row is at or past the visible rows returns before it loads anything and writes nothing, and the merge of the splits counts the
+ *     splits that ran and reads only those.  A captured call replays correctly for every later pair of lengths.
+ *   - the library only READS the two words; the caller advances the residual word by new_rows in stream order after the call (inside
+ *     a captured region: a device-side add) and, when it moves residual rows onto the tail (kvc_quantize_rows at row0 = Tq, between
+ *     two replays), adds their number to the tail word and takes it off the residual word.
+ *   - the clamps: no value of either word makes a kernel read or write outside the buffers.  Codes, metadata and residual rows behind
+ *     the visible rows are neither read nor written (key metadata is read per group of a visible row).
+ *   - arithmetic: kvc_decode_step_quant's.  When Tq == qtail->capacity and Rr + new_rows == res_capacity the two plans coincide and
+ *     `out` and the appended residual rows are kvc_decode_step_quant's bit for bit.
+ *   - workspace: kvc_decode_quant_dev_workspace_bytes(p, prefix, qtail) bytes, 16-byte aligned, sized from the bound; less (or NULL)
+ *     only reduces the number of splits.  Its contents before the call do not matter.  A captured call must own its workspace (and
+ *     `out`) for as long as the graph lives.
+ * No outliers (the KVQuant form keeps host-read pool counters).  Every argument is checked before any pointer is used: everything
+ * kvc_decode_step_quant checks (with the two ignored lengths taken as 0), a NULL word, res_capacity < new_rows and a qtail->capacity
+ * that is not a multiple of group_size (KVC_ERR_INVALID).  Enqueue-only: no allocation, no synchronisation, no host read, no kernel
+ * attribute set on the launch path. */
+size_t kvc_decode_quant_dev_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail);
+int kvc_decode_step_quant_dev(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix, const kvc_quant_seg* qtail,
+                              const int32_t* qtail_rows_dev /* device, 1 int32 */, const int32_t* res_rows_dev /* device, 1 int32 */,
+                              const void* q, const void* k_new, const void* v_new, void* k_res, void* v_res, void* out,
+                              void* workspace /* nullable */, size_t workspace_bytes, void* hip_stream);
+
 /* ---- quantized cache with exact outliers (KVQuant-style "dense-and-sparse", --quant_method kvquant) ------------------------
  * Split: T' = threshold rounded to dtype (round to nearest even; fp32 uses it as is).  Element x is an OUTLIER iff x < -T' or
  * x > T' (so +-inf are outliers and NaN is not).  The DENSE input is x with every outlier replaced by +0; its codes and metadata

@@ -11,7 +11,7 @@ there is no CPU or eager-PyTorch fallback: if the extension is missing the impor
 __version__ = "0.1.0"
 __all__ = ["QuantizedCompressedCache", "QuantizedCompressedLayer", "KVQuantCompressedCache", "KVQuantCompressedLayer",
            "DecodeCompressedCache", "DecodeCompressedLayer", "HeavyHitterCache", "HeavyHitterLayer", "GraphDecoder",
-           "BoundedDeviceLayer", "BoundedHeavyHitterLayer"]
+           "BoundedDeviceLayer", "BoundedHeavyHitterLayer", "QuantizedDeviceLayer"]
 
 
 def __getattr__(name):

@@ -33,7 +33,8 @@ EXPORTS = ("kvc_version", "kvc_last_error", "kvc_workspace_bytes", "kvc_compress
            "kvc_decode_compress_workspace_bytes", "kvc_decode_compress", "kvc_decode_rows_workspace_bytes",
            "kvc_decode_step_rows", "kvc_decode_scored_workspace_bytes", "kvc_decode_step_scored",
            "kvc_decode_evict_workspace_bytes", "kvc_decode_evict", "kvc_decode_dev_workspace_bytes", "kvc_decode_step_dev",
-           "kvc_decode_step_dev_ring", "kvc_decode_dev_scored_workspace_bytes", "kvc_decode_step_dev_scored")
+           "kvc_decode_step_dev_ring", "kvc_decode_dev_scored_workspace_bytes", "kvc_decode_step_dev_scored",
+           "kvc_decode_quant_dev_workspace_bytes", "kvc_decode_step_quant_dev")
 
 
 class KvcError(RuntimeError):
@@ -187,6 +188,9 @@ def lib():
         L.kvc_decode_quant_workspace_bytes.argtypes = [dq, qs, qs]
         L.kvc_decode_quant_workspace_bytes.restype = sz
         L.kvc_decode_step_quant.argtypes = [dq, qs, qs] + [vp] * 7 + [sz, vp]
+        L.kvc_decode_quant_dev_workspace_bytes.argtypes = [dq, qs, qs]
+        L.kvc_decode_quant_dev_workspace_bytes.restype = sz
+        L.kvc_decode_step_quant_dev.argtypes = [dq, qs, qs] + [vp] * 9 + [sz, vp]
         qo = ctypes.POINTER(QuantOutliers)
         L.kvc_quantize_rows_outliers.argtypes = [qp, ctypes.c_float, vp, vp, vp, qo, vp]
         L.kvc_dequantize_rows_outliers.argtypes = [qp, vp, vp, qo, vp, vp]
@@ -914,6 +918,86 @@ def decode_step_quant(q, k_new, v_new, prefix, qtail, k_res, v_res, res_rows, sc
     ws = workspace(dev, nbytes) if nbytes else None
     _check(_call(dev, L.kvc_decode_step_quant, ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st), _ptr(q), _ptr(k_new), _ptr(v_new),
                  _ptr(k_res), _ptr(v_res), _ptr(out), _ptr(ws), nbytes, _stream(dev)))
+    return out
+
+
+_QDEV_PLANS = {}                                         # layout key -> (DecodeQuantParams, workspace bytes) of decode_step_quant_dev
+
+
+def _seg_key(seg):
+    return None if seg is None else tuple((x.shape, x.stride()) for x in seg[:4]) + (seg[4],)
+
+
+def decode_quant_dev_plan(q, k_new, prefix, qtail, k_res, nbits, group_size, residual_length, out_strides=None):
+    """(kvc_decode_quant_params, workspace bytes) of decode_step_quant_dev for this layout, built once per (layout, capacities) and
+    reused: between calls only pointers change.  prefix: (k_codes, v_codes, k_meta, v_meta, rows) with the prompt's rows; qtail: the
+    same tuple, its last entry ignored (the segment's capacity is what its buffers hold).  out_strides: (b, h, l) strides of a
+    caller-owned `out`, None = a dense [b, t, H_q, D]."""
+    b, hq, t, D = q.shape
+    if out_strides is None:
+        out_strides = (t * hq * D, D, hq * D)
+    pk, tk = _seg_key(prefix), _seg_key(qtail)
+    key = (q.dtype, q.device, b, hq, k_new.shape[1], t, D, nbits, group_size, residual_length, pk, tk and tk[:4], k_res.shape[2],
+           q.stride(), k_new.stride(), k_res.stride(0), k_res.stride(1), out_strides)
+    plan = _QDEV_PLANS.get(key)
+    if plan is None:
+        if len(_QDEV_PLANS) >= 256:
+            _QDEV_PLANS.clear()
+        p = DecodeQuantParams()
+        p.dtype, p.bsz, p.n_q_heads, p.n_kv_heads, p.head_dim = DTYPES[q.dtype], b, hq, k_new.shape[1], D
+        p.nbits, p.group_size, p.residual_length = nbits, group_size, residual_length
+        p.res_rows, p.res_capacity, p.new_rows = 0, k_res.shape[2], t
+        p.q_stride_b, p.q_stride_h, p.q_stride_l = q.stride(0), q.stride(1), q.stride(2)
+        p.new_stride_b, p.new_stride_h, p.new_stride_l = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+        p.res_stride_b, p.res_stride_h = k_res.stride(0), k_res.stride(1)
+        p.out_stride_b, p.out_stride_h, p.out_stride_l = out_strides
+        p.scaling = 1.0                                  # checked with the layout; the call writes its own
+        sp, st = _quant_seg(prefix), _quant_seg(qtail)
+        st.rows = 0
+        nbytes = lib().kvc_decode_quant_dev_workspace_bytes(ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st))
+        err = lib().kvc_last_error().decode()
+        if nbytes == 0 and err:
+            raise KvcError(ERR_INVALID, err)
+        plan = _QDEV_PLANS[key] = (p, nbytes)
+    return plan
+
+
+def decode_step_quant_dev(q, k_new, v_new, prefix, qtail, k_res, v_res, qtail_counter, res_counter, scaling, nbits, group_size,
+                          residual_length, ws=None, out=None):
+    """One decode step over the quantized cache whose two growing lengths live on the device (kvc_decode_step_quant_dev):
+    decode_step_quant, except that the quantized tail holds Tq = clamp(qtail_counter[0], 0, capacity) rows (capacity: what the
+    buffers of `qtail` hold; the tuple's row count is ignored), the step's rows are appended at residual row
+    Rr = clamp(res_counter[0], 0, res capacity - t) of k_res / v_res [b, H_kv, res capacity, D] and token i sees the prefix, tail rows
+    [0, Tq) and residual rows [0, Rr + i + 1).  Both counters: int32 [1] on the device, only read.  Nothing passed to the library
+    depends on Tq or Rr, so a captured call replays for every later pair of lengths.  ws / out: as decode_step_dev — a captured
+    call must own both (decode_quant_dev_plan(...)[1] bytes)."""
+    segs = (*(prefix[:4] if prefix else ()), *(qtail[:4] if qtail else ()))
+    _require_gpu(q, k_new, v_new, k_res, v_res, qtail_counter, res_counter, *segs)
+    dev = _one_device(q, k_new, v_new, k_res, v_res, qtail_counter, res_counter, ws, out, *segs)
+    q, k_new, v_new = _last_dim_contig(q), _last_dim_contig(k_new), _last_dim_contig(v_new)
+    if k_new.stride() != v_new.stride():
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    b, hq, t, D = q.shape
+    for c in (qtail_counter, res_counter):
+        assert c.dtype == torch.int32 and c.numel() == 1
+    assert k_new.shape == v_new.shape and k_new.shape[2] == t and k_res.stride() == v_res.stride() and k_res.shape == v_res.shape
+    assert k_res.stride(3) == 1 and k_res.stride(2) == D, "residual rows must be dense"
+    if out is None:
+        out = torch.empty(b, t, hq, D, dtype=q.dtype, device=dev)
+    else:
+        assert out.shape == (b, t, hq, D) and out.dtype == q.dtype and out.stride(3) == 1
+    p, nbytes = decode_quant_dev_plan(q, k_new, prefix, qtail, k_res, nbits, group_size, residual_length,
+                                      (out.stride(0), out.stride(2), out.stride(1)))
+    p.scaling = scaling
+    if ws is None:
+        ws = workspace(dev, nbytes) if nbytes else None
+    else:
+        assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    sp, st = _quant_seg(prefix), _quant_seg(qtail)
+    st.rows = 0
+    _check(_call(dev, lib().kvc_decode_step_quant_dev, ctypes.byref(p), ctypes.byref(sp), ctypes.byref(st), _ptr(qtail_counter),
+                 _ptr(res_counter), _ptr(q), _ptr(k_new), _ptr(v_new), _ptr(k_res), _ptr(v_res), _ptr(out), _ptr(ws),
+                 ws.numel() if ws is not None else 0, _stream(dev)))
     return out
 
 

@@ -1281,6 +1281,202 @@ class QuantizedCompressedCache(Cache):
         super().__init__(layers=[QuantizedCompressedLayer(nbits, q_group_size, residual_length) for _ in range(text.num_hidden_layers)])
 
 
+def quant_flush(res_rows, tail_rows, capacity, residual_length):
+    """QuantizedCompressedLayer's flush rule for one-token steps on a quantized tail of FIXED capacity, from host integers alone:
+    -> (rows that move from the residual onto the tail now, times the tail's capacity must double first).  The residual is flushed
+    whole once it holds residual_length rows (a multiple of the group size, so nothing stays behind)."""
+    if res_rows < residual_length:
+        return 0, 0
+    doublings = 0
+    while tail_rows + res_rows > capacity:
+        capacity, doublings = 2 * capacity, doublings + 1
+    return res_rows, doublings
+
+
+def quant_schedule(residual_length, capacity, steps):
+    """What `steps` one-token steps do to a QuantizedDeviceLayer whose tail starts empty with `capacity` rows: -> (the steps (from 1)
+    after which the residual is flushed, the tail rows after each flush, the grow events, the captures of a decoder that captures
+    before the first step and again before the first step after every grow event).  Host arithmetic only."""
+    flushes, tails, grows, captures = [], [], 0, 0
+    res = tail = 0
+    stale = True
+    for step in range(1, steps + 1):
+        if stale:
+            captures, stale = captures + 1, False
+        res += 1
+        rows, doublings = quant_flush(res, tail, capacity, residual_length)
+        if rows:
+            if doublings:
+                capacity, grows, stale = capacity << doublings, grows + 1, True
+            tail, res = tail + rows, 0
+            flushes.append(step)
+            tails.append(tail)
+    return flushes, tails, grows, captures
+
+
+class QuantizedDeviceLayer(_FixedBuffersLayer):
+    """The quantized (KIVI-style) cache in DEVICE-LENGTH MODE (graph_decode.GraphDecoder(model, nbits=N)): QuantizedCompressedLayer's
+    segments and flush rule on buffers that keep their addresses between grow events, so that a captured step replays while rows are
+    decoded and quantized.  One sequence (bsz = 1), one-token steps.
+
+    PREFIX — the compressed prompt, quantized eagerly at adoption by the rule of QuantizedCompressedLayer._set_prefix (the
+    full-precision prompt buffers are dropped);  QUANTIZED TAIL — a segment of fixed capacity (a multiple of residual_length) whose
+    rows in use live in a device int32 (`_tword`);  RESIDUAL — exactly residual_length full-precision rows per KV head whose rows in
+    use live in a second device int32 (`_rword`), advanced by the owner's in-graph add.  The step (kvc_decode_step_quant_dev) reads
+    both words and has its own workspace and output buffer.
+
+    `_trows` / `_rrows` / `true_length` are the host MIRROR, advanced by the owner (`advance`), who then calls `maybe_flush`: once
+    the mirror says the residual holds residual_length rows they are quantized onto the tail eagerly on the step's stream
+    (kvc_quantize_rows for keys and for values, row0 from the mirror), then the tail word += rows and the residual word = 0 by device
+    ops.  When the tail cannot take them its capacity doubles first (codes and metadata in use are copied as they are) and
+    `maybe_flush` says so: graphs captured over the old buffers are stale.  Nothing is read from the device."""
+
+    def __init__(self, nbits=4, q_group_size=64, residual_length=128):
+        _check_quant_args(nbits, q_group_size, residual_length)
+        super().__init__()
+        self.nbits, self.group_size, self.residual_length = nbits, q_group_size, residual_length
+        self._clear_quant()
+
+    def _clear_quant(self):
+        self._pkc = self._pvc = self._pkm = self._pvm = None     # prefix: codes [1, H_q, P, D*nbits/8], metadata (kvc.h)
+        self._tkc = self._tvc = self._tkm = self._tvm = None     # quantized tail [1, H_kv, capacity, ...]
+        self._rk = self._rv = None                               # residual [1, H_kv, residual_length, D], full precision
+        self._prows = self._trows = self._rrows = 0
+        self._tword = self._rword = None                         # int32 [1] each, on the device: tail rows / residual rows in use
+        self._out = None                                         # the step's own output buffer
+        self.flushes = 0
+
+    def reset(self):
+        super().reset()
+        self._clear_quant()
+
+    _after_step = "maybe_flush"
+    _qview = QuantizedCompressedLayer._qview
+    _dequant = QuantizedCompressedLayer._dequant
+    keys = property(lambda self: self._qview("k"), _placeholder_only("keys"))
+    values = property(lambda self: self._qview("v"), _placeholder_only("values"))
+
+    @classmethod
+    def adopt(cls, layer, nbits, q_group_size, residual_length, tail_rows, tail_word, res_word, n_kv_heads):
+        """The quantized layer that takes over from `layer`, a plain CompressedDynamicLayer right after its prefill: its rows are
+        quantized into the prefix.  tail_rows: the quantized tail's first capacity, a multiple of residual_length.  tail_word /
+        res_word: int32 [1] each on the layer's device, this layer's own; both are set to 0 here by device ops."""
+        if type(layer) is not CompressedDynamicLayer or layer._kbuf is None:
+            raise NotImplementedError(f"kvcache_factory_amd: QuantizedDeviceLayer adopts a prefilled CompressedDynamicLayer, not a "
+                                      f"{type(layer).__name__}")
+        if layer._split or layer._stored != layer._pmax or layer._devlen:
+            raise NotImplementedError("kvcache_factory_amd: this layer already holds decoded rows; enter the quantized mode right after "
+                                      "the prefill")
+        b, hq, _, d = layer._kbuf.shape
+        if b != 1 or layer._padded:
+            raise NotImplementedError(f"kvcache_factory_amd: the fused quantized step holds one sequence (bsz = 1), got a batch of {b}")
+        self = cls(nbits, q_group_size, residual_length)
+        if tail_rows < residual_length or tail_rows % residual_length:
+            raise ValueError(f"tail_rows must be a positive multiple of residual_length ({residual_length}), got {tail_rows}")
+        for w in (tail_word, res_word):
+            assert w.dtype == torch.int32 and w.numel() == 1 and w.device == layer._kbuf.device
+        from . import _kvc
+        P, dt, dev = layer._stored, layer._kbuf.dtype, layer._kbuf.device
+        self.dtype, self.device, self.is_initialized = layer.dtype, layer.device, True
+        self.true_length = layer.true_length
+        bufs = _kvc.quant_buffers(1, hq, P, d, nbits, q_group_size, dev)
+        self._quantize_into(layer._kbuf[:, :, :P], layer._vbuf[:, :, :P], bufs, 0)
+        self._pkc, self._pvc, self._pkm, self._pvm = bufs
+        self._prows = P
+        self._tkc, self._tvc, self._tkm, self._tvm = _kvc.quant_buffers(1, n_kv_heads, tail_rows, d, nbits, q_group_size, dev)
+        self._rk = torch.empty(1, n_kv_heads, residual_length, d, dtype=dt, device=dev)
+        self._rv = torch.empty_like(self._rk)
+        self._tword, self._rword = tail_word, res_word
+        tail_word.zero_()
+        res_word.zero_()
+        self._split, self._devlen, self._dev_hold = True, True, True
+        return self
+
+    def _quantize_into(self, k, v, bufs, row0):
+        from . import _kvc
+        kc, vc, km, vm = bufs
+        _kvc.quantize_rows(k, kc, km, row0, _kvc.QUANT_KEYS, self.nbits, self.group_size)
+        _kvc.quantize_rows(v, vc, vm, row0, _kvc.QUANT_VALUES, self.nbits, self.group_size)
+
+    # ---- the lengths of the host mirror ----------------------------------------------------------------------------------------
+    def rows(self):
+        """(P, Tq, Rr) of the host mirror."""
+        return self._prows, self._trows, self._rrows
+
+    def tail_capacity(self):
+        return 0 if self._tkc is None else self._tkc.shape[2]
+
+    def segments(self):
+        """((k_codes, v_codes, k_meta, v_meta, rows) of the prefix, of the quantized tail, (k_res, v_res, rows)): the buffers as they
+        are, rows from the mirror."""
+        return ((self._pkc, self._pvc, self._pkm, self._pvm, self._prows), (self._tkc, self._tvc, self._tkm, self._tvm, self._trows),
+                (self._rk, self._rv, self._rrows))
+
+    def advance(self, t):
+        """t rows were appended to the residual by a step whose Python did not count them (a replayed graph): the mirror follows."""
+        self._rrows += t
+        self.true_length += t
+
+    def can_split(self):
+        return self._pkc is not None
+
+    def stored_length(self):
+        return self._prows + self._trows + self._rrows
+
+    # ---- the step -----------------------------------------------------------------------------------------------------------------
+    def _decode_attend_dev(self, query_states, key_states, value_states, scaling):
+        from . import _kvc
+        b, _, t, _ = key_states.shape
+        if b != 1 or t != 1:
+            raise NotImplementedError(f"kvcache_factory_amd: a QuantizedDeviceLayer takes one-token steps of one sequence, got {b} x {t}")
+        if self._rrows + t > self.residual_length:
+            raise RuntimeError(f"kvcache_factory_amd: the residual holds {self._rrows} of {self.residual_length} rows: the owner did "
+                               "not call maybe_flush() after the last step")
+        pre, qt = (self._pkc, self._pvc, self._pkm, self._pvm, self._prows), (self._tkc, self._tvc, self._tkm, self._tvm, 0)
+        key = (self._tkc.shape[2], query_states.stride(), key_states.stride())
+        if self._dev_ws_key != key:                                   # once per capacity: the step's own workspace and output
+            nbytes = _kvc.decode_quant_dev_plan(query_states, key_states, pre, qt, self._rk, self.nbits, self.group_size,
+                                                self.residual_length)[1]
+            self._dev_ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self._rk.device)
+            if self._out is None:
+                self._out = torch.empty(b, t, query_states.shape[1], query_states.shape[3], dtype=query_states.dtype,
+                                        device=self._rk.device)
+            self._dev_ws_key = key
+        out = _kvc.decode_step_quant_dev(query_states, key_states, value_states, pre, qt, self._rk, self._rv, self._tword, self._rword,
+                                         scaling, self.nbits, self.group_size, self.residual_length, ws=self._dev_ws, out=self._out)
+        if not self._dev_hold:
+            self.advance(t)
+        return out
+
+    def _grow(self):
+        """A quantized tail of twice the capacity; codes and metadata in use are copied as they are."""
+        from . import _kvc
+        G = self.group_size
+        old = (self._tkc, self._tvc, self._tkm, self._tvm)
+        _, h, cap, cb = self._tkc.shape
+        bufs = _kvc.quant_buffers(1, h, 2 * cap, cb * 8 // self.nbits, self.nbits, G, self._tkc.device)
+        if self._trows:
+            for new, was, rows in zip(bufs, old, (self._trows, self._trows, self._trows // G, self._trows)):
+                new[:, :, :rows].copy_(was[:, :, :rows])
+        self._tkc, self._tvc, self._tkm, self._tvm = bufs
+        self._dev_ws = self._dev_ws_key = None
+
+    def maybe_flush(self):
+        """The flush rule, from the host mirror, after the owner advanced it for a step.  -> (whether the residual was flushed,
+        whether the tail grew — graphs captured before are stale then)."""
+        rows, doublings = quant_flush(self._rrows, self._trows, self._tkc.shape[2], self.residual_length)
+        if not rows:
+            return False, False
+        for _ in range(doublings):
+            self._grow()
+        self._quantize_into(self._rk[:, :, :rows], self._rv[:, :, :rows], (self._tkc, self._tvc, self._tkm, self._tvm), self._trows)
+        self._tword.add_(rows)
+        self._rword.zero_()
+        self._trows, self._rrows = self._trows + rows, 0
+        self.flushes += 1
+        return True, doublings > 0
+
+
 class RaggedDynamicLayer(_BatchOps, DynamicLayer):
     """The flattened cache of AdaKV / HeadKV for one layer — counterpart of the reference's DynamicCacheSplitHeadFlatten
     (pyramidkv_utils.py:28-102), whose every decode step allocates a new tensor and re-copies the whole cache with one row

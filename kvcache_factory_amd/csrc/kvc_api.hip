@@ -859,6 +859,98 @@ __attribute__((visibility("default"))) int kvc_decode_step_quant(const kvc_decod
 }
 }  // extern "C"
 
+// ---- the device-counted quantized decode step (kvc_decode_quant_dev.hip) --------------------------------------------------
+namespace {
+// kvc_decode_step_quant's checks with the two lengths left to the device, and those of the capacities that bound them
+int decode_quant_dev_check(const kvc_decode_quant_params* p, const kvc_quant_seg* pre, const kvc_quant_seg* qt) {
+    if (!p) return fail(KVC_ERR_INVALID, "params is NULL");
+    if (!qt) return fail(KVC_ERR_INVALID, "quantized tail segment is NULL");
+    kvc_decode_quant_params c = *p;
+    kvc_quant_seg t = *qt;
+    c.res_rows = 0;                                                   // ignored here: the device counts
+    t.rows = 0;
+    if (p->new_rows >= 1 && p->res_capacity < p->new_rows)
+        return fail(KVC_ERR_INVALID, "res_capacity %d holds fewer rows than the step's new_rows %d", p->res_capacity, p->new_rows);
+    if (int rc = decode_quant_check(&c, pre, &t)) return rc;
+    if (qt->capacity % p->group_size)
+        return fail(KVC_ERR_INVALID, "quantized tail capacity %d not a multiple of group_size %d", qt->capacity, p->group_size);
+    if ((int64_t)pre->rows + qt->capacity + p->res_capacity > 0x7fffffffLL)
+        return fail(KVC_ERR_INVALID, "prefix rows + tail capacity + res_capacity overflows int32");
+    return KVC_OK;
+}
+int decode_quant_dev_splits(const kvc_decode_quant_params* p, const kvc_quant_seg* pre, const kvc_quant_seg* qt) {
+    return kvc::decode_splits(p->bsz, p->n_q_heads, p->new_rows, pre->rows + qt->capacity + p->res_capacity);    // the bound
+}
+}  // namespace
+
+extern "C" {
+__attribute__((visibility("default"))) size_t kvc_decode_quant_dev_workspace_bytes(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix,
+                                                                                   const kvc_quant_seg* qtail) {
+    if (decode_quant_dev_check(p, prefix, qtail)) return 0;
+    g_err[0] = 0;
+    return kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, decode_quant_dev_splits(p, prefix, qtail));
+}
+
+__attribute__((visibility("default"))) int kvc_decode_step_quant_dev(const kvc_decode_quant_params* p, const kvc_quant_seg* prefix,
+                                                                     const kvc_quant_seg* qtail, const int32_t* qtail_rows_dev,
+                                                                     const int32_t* res_rows_dev, const void* q, const void* k_new,
+                                                                     const void* v_new, void* k_res, void* v_res, void* out, void* workspace,
+                                                                     size_t workspace_bytes, void* hip_stream) {
+    if (int rc = decode_quant_dev_check(p, prefix, qtail)) return rc;
+    if (!qtail_rows_dev || !res_rows_dev) return fail(KVC_ERR_INVALID, "qtail_rows_dev / res_rows_dev is NULL");
+    if (((uintptr_t)qtail_rows_dev) % 4 || ((uintptr_t)res_rows_dev) % 4)
+        return fail(KVC_ERR_ALIGNMENT, "qtail_rows_dev / res_rows_dev is not 4-byte aligned");
+    if (!q || !k_new || !v_new || !k_res || !v_res || !out)
+        return fail(KVC_ERR_INVALID, "q, k_new, v_new, k_res, v_res and out must be non-NULL");
+    if (prefix->rows > 0 && (!prefix->k_codes || !prefix->v_codes || !prefix->k_meta || !prefix->v_meta))
+        return fail(KVC_ERR_INVALID, "a prefix with rows needs its codes and metadata");
+    if (qtail->capacity > 0 && (!qtail->k_codes || !qtail->v_codes || !qtail->k_meta || !qtail->v_meta))
+        return fail(KVC_ERR_INVALID, "a quantized tail with capacity needs its codes and metadata");
+    const int es = esize_of(p->dtype);
+    const void* ptrs[] = {q, k_new, v_new, k_res, v_res, out, workspace, prefix->k_codes, prefix->v_codes, prefix->k_meta, prefix->v_meta,
+                          qtail->k_codes, qtail->v_codes, qtail->k_meta, qtail->v_meta};
+    for (const void* ptr : ptrs) if (((uintptr_t)ptr) % 16) return fail(KVC_ERR_ALIGNMENT, "a pointer is not 16-byte aligned");
+    const int64_t strides[] = {p->q_stride_b, p->q_stride_h, p->q_stride_l, p->new_stride_b, p->new_stride_h, p->new_stride_l,
+                               p->res_stride_b, p->res_stride_h};
+    for (int64_t sd : strides) if ((sd * es) % 16) return fail(KVC_ERR_ALIGNMENT, "a stride is not a multiple of 16 bytes");
+    kvc::DecodeArgs ap;                                           // the step's rows -> the residual
+    std::memset(&ap, 0, sizeof(ap));
+    ap.k_new = k_new; ap.v_new = v_new; ap.k_tail = k_res; ap.v_tail = v_res;
+    ap.new_stride_b = p->new_stride_b; ap.new_stride_h = p->new_stride_h; ap.new_stride_l = p->new_stride_l;
+    ap.tail_stride_b = p->res_stride_b; ap.tail_stride_h = p->res_stride_h;
+    ap.bsz = p->bsz; ap.n_q_heads = p->n_q_heads; ap.n_kv_heads = p->n_kv_heads; ap.group = p->n_q_heads / p->n_kv_heads;
+    ap.new_rows = p->new_rows; ap.esize = es; ap.row_bytes = p->head_dim * es;
+    kvc::DecodeQDevArgs da;
+    std::memset(&da, 0, sizeof(da));
+    kvc::DecodeQArgs& a = da.a;
+    a.q = q; a.k_res = k_res; a.v_res = v_res; a.out = out;
+    a.q_stride_b = p->q_stride_b; a.q_stride_h = p->q_stride_h; a.q_stride_l = p->q_stride_l;
+    a.res_stride_b = p->res_stride_b; a.res_stride_h = p->res_stride_h;
+    a.out_stride_b = p->out_stride_b; a.out_stride_h = p->out_stride_h; a.out_stride_l = p->out_stride_l;
+    kvc::QSegArgs* dst[2] = {&a.pre, &a.qt};
+    const kvc_quant_seg* src[2] = {prefix, qtail};
+    for (int k = 0; k < 2; ++k) {
+        kvc::QSegArgs& d = *dst[k];
+        const kvc_quant_seg& s = *src[k];
+        d.kc = s.k_codes; d.vc = s.v_codes; d.km = s.k_meta; d.vm = s.v_meta; d.rows = k == 0 ? s.rows : 0;    // qtail->rows is ignored
+        d.c_stride_b = s.code_stride_b; d.c_stride_h = s.code_stride_h;
+        d.km_stride_b = s.k_meta_stride_b; d.km_stride_h = s.k_meta_stride_h; d.vm_stride_b = s.v_meta_stride_b; d.vm_stride_h = s.v_meta_stride_h;
+    }
+    a.bsz = p->bsz; a.n_q_heads = p->n_q_heads; a.group = p->n_q_heads / p->n_kv_heads; a.gsize = p->group_size;
+    a.new_rows = p->new_rows; a.scaling = p->scaling;                 // p->res_rows is ignored: the device counts
+    da.qt_dev = qtail_rows_dev; da.res_dev = res_rows_dev; da.qt_capacity = qtail->capacity; da.res_capacity = p->res_capacity;
+    a.splits = 1;
+    if (workspace) {                                                  // as many splits of the BOUND as the workspace can hold
+        int s = decode_quant_dev_splits(p, prefix, qtail);
+        while (s > 1 && kvc::decode_part_bytes(p->bsz, p->n_q_heads, p->new_rows, p->head_dim, s) > workspace_bytes) --s;
+        a.splits = s; a.part = static_cast<float*>(workspace);
+    }
+    if (int rc = kvc::launch_decode_step_quant_dev(da, p->dtype, p->head_dim, p->nbits, ap, static_cast<hipStream_t>(hip_stream)))
+        return fail(rc, "no device-counted quantized decode kernel for dtype %d head_dim %d nbits %d", p->dtype, p->head_dim, p->nbits);
+    return hip_ok("device-counted quantized decode step launch");
+}
+}  // extern "C"
+
 // ---- quantized cache with exact outliers (kvc_quant.hip) -----------------------------------------------------------------
 namespace {
 constexpr int32_t kOutlPoolMax = (1 << 24) - 1;            // rowinfo keeps the first entry in 24 bits

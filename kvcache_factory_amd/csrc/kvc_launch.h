@@ -205,6 +205,13 @@ struct DecodeQArgs {       // kvc_decode_step_quant: quantized prefix + quantize
     float* part; int splits, rows_per_split;          // as DecodeArgs: (m, l, acc[D]) per (b, h, token, split)
 };
 
+struct DecodeQDevArgs {    // kvc_decode_quant_dev.hip: DecodeQArgs (qt.rows and res_rows unused) + the lengths the device reads
+    DecodeQArgs a;
+    const int32_t* qt_dev;                            // 1 int32, device: rows of the quantized tail in use
+    const int32_t* res_dev;                           // 1 int32, device: residual rows before this step
+    int qt_capacity, res_capacity;                    // rows the tail segment / the residual buffers hold (the clamps of the words)
+};
+
 struct OutlArgs {          // one outlier pool (include/kvc.h, kvc_quant_outliers) and the split threshold (already rounded to dtype)
     uint8_t* chan; void* val; int32_t* used; uint32_t* rowinfo;
     int64_t pool_stride_b, ri_stride_b, ri_stride_h;
@@ -307,6 +314,7 @@ int decode_dev_splits(int bsz, int n_q_heads, int new_rows, int rows);
 int launch_quantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_dequantize(const QuantArgs& a, int dtype, int nbits, int mode, hipStream_t st);
 int launch_decode_step_quant(DecodeQArgs a, int dtype, int head_dim, int nbits, const DecodeArgs& append, hipStream_t st);
+int launch_decode_step_quant_dev(DecodeQDevArgs a, int dtype, int head_dim, int nbits, const DecodeArgs& append, hipStream_t st);   // kvc_decode_quant_dev.hip
 int launch_quantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st);
 int launch_dequantize_outliers(const QuantArgs& a, const OutlArgs& o, int dtype, int nbits, int mode, hipStream_t st);
 int launch_decode_step_quant_outliers(DecodeQArgs a, const DecodeOArgs& o, int dtype, int head_dim, int nbits, const DecodeArgs& append,

@@ -30,12 +30,21 @@ whether a compression runs — eagerly, between two replays, on the same stream.
 is the same for H2O's own decode-time rule (HeavyHitterCache's): the prompt goes through an internal HeavyHitterCache, every layer is
 then a cache.BoundedHeavyHitterLayer whose captured step (kvc_decode_step_dev_scored) accumulates the scores, and every `heavy_hitter`
 tokens the mirrors have each layer evict its lowest-scoring rows between two replays.  One capture, no growth, no host read.
+
+    dec = GraphDecoder(model, nbits=4, q_group_size=64, residual_length=128, tail_rows=1024)      # one sequence
+
+replays the quantized (KIVI-style) cache, QuantizedCompressedCache's rule on cache.QuantizedDeviceLayer: the prompt is quantized once
+when the layers are adopted, the captured step (kvc_decode_step_quant_dev) reads the rows of the quantized tail and of the residual
+from two device words per layer, and an in-graph add advances the residual words.  Every `residual_length` tokens the mirrors have
+each layer quantize its residual onto the tail between two replays; `tail_rows` (rounded up to a multiple of `residual_length`) is the
+tail's first capacity, doubled — with a new capture — when the next flush would not fit.
 """
 import torch
 
 from . import pyramidkv_utils as pu
 from .cache import (DECODE_METHODS, BoundedDeviceLayer, BoundedHeavyHitterLayer, CompressedDynamicLayer, DecodeCompressedCache,
-                    HeavyHitterCache, HeavyHitterLayer, QuantizedCompressedCache, _check_interval, decode_budget, heavy_hitter_budget)
+                    HeavyHitterCache, HeavyHitterLayer, QuantizedCompressedCache, QuantizedDeviceLayer, _check_interval,
+                    _check_quant_args, decode_budget, heavy_hitter_budget)
 
 _OWN_LAYOUT = ("adakv", "headkv", "think")
 
@@ -55,7 +64,8 @@ def tails_needed(capacity, tail, t):
 class GraphDecoder:
     WARMUP = 2                          # eager steps of the same code before a capture (lazy initialisations, workspaces, plans)
 
-    def __init__(self, model, tail_rows=256, capture=True, interval=None, heavy_hitter=None):
+    def __init__(self, model, tail_rows=256, capture=True, interval=None, heavy_hitter=None, nbits=None, q_group_size=64,
+                 residual_length=128):
         if isinstance(tail_rows, bool) or not isinstance(tail_rows, int) or tail_rows < 1:
             raise ValueError(f"tail_rows must be an int >= 1, got {tail_rows!r}")
         if interval is not None:
@@ -66,15 +76,23 @@ class GraphDecoder:
             if interval is not None:
                 raise ValueError("kvcache_factory_amd: GraphDecoder takes interval= (snapkv / pyramidkv / streamingllm) or "
                                  "heavy_hitter= (h2o), not both")
+        if nbits is not None:
+            _check_quant_args(nbits, q_group_size, residual_length)
+            if interval is not None or heavy_hitter is not None:
+                raise ValueError("kvcache_factory_amd: GraphDecoder takes nbits= (the quantized cache) or interval= / heavy_hitter= "
+                                 "(a bounded cache), not both")
+            tail_rows = -(-tail_rows // residual_length) * residual_length   # the quantized tail takes whole residuals
         self.model, self.tail_rows, self.capture, self.interval, self.heavy_hitter = model, tail_rows, bool(capture), interval, heavy_hitter
+        self.nbits, self.q_group_size, self.residual_length = nbits, q_group_size, residual_length
         self.config = model.config.get_text_config() if hasattr(model.config, "get_text_config") else model.config
         self._refuse_model()
         self._clusters()
+        self._refuse_quant()
         self.captures = 0               # graphs captured since the last prefill
         self.grows = 0                  # times the tails were doubled since the last prefill
         self._cache = self._graph = None
         self._layers = ()
-        self._tok = self._pos = self._logits = self._counter = None
+        self._tok = self._pos = self._logits = self._counter = self._stepped = None
 
     # ---- refusals: all raised before anything is stored or captured --------------------------------------------------------------
     def _attn(self):
@@ -128,6 +146,18 @@ class GraphDecoder:
             decode_budget(clusters[-1], self.interval)
         return clusters
 
+    def _refuse_quant(self):
+        """nbits mode: the pivot merge has no quantized decode cache here (every layer's kv_cluster as the patched forward builds it)."""
+        if self.nbits is None:
+            return
+        from .attention import _INIT
+        for block in self.model.model.layers:
+            _INIT[self.method](block.self_attn)
+            merge = getattr(block.self_attn.kv_cluster, "merge", None)
+            if merge is not None:
+                raise NotImplementedError(f"kvcache_factory_amd: {self.method} with merge={merge!r} is not replayed over the quantized "
+                                          "cache; GraphDecoder(nbits=...) needs merge=None")
+
     def _refuse_call(self, input_ids, cache):
         for kind, why in ((QuantizedCompressedCache, "a quantized cache (QuantizedCompressedCache / KVQuantCompressedCache) quantizes "
                                                      "its tail on a host-counted schedule"),
@@ -161,7 +191,15 @@ class GraphDecoder:
         from .attention import _pending_for
         self._refuse_call(input_ids, past_key_values)
         clusters = self._clusters()
-        heavy = self.heavy_hitter is not None
+        self._refuse_quant()
+        heavy, quant = self.heavy_hitter is not None, self.nbits is not None
+        if quant:
+            if past_key_values is not None:
+                raise ValueError("kvcache_factory_amd: GraphDecoder(nbits=...) builds its own quantized cache; past_key_values must "
+                                 f"be None, got a {type(past_key_values).__name__}")
+            if input_ids.shape[0] != 1:
+                raise NotImplementedError("kvcache_factory_amd: the fused quantized step has no batched form; "
+                                          f"GraphDecoder(nbits=...) decodes one sequence, got a batch of {input_ids.shape[0]}")
         if clusters is not None:
             mode = "heavy_hitter" if heavy else "interval"
             if past_key_values is not None:
@@ -196,7 +234,15 @@ class GraphDecoder:
             if type(layer) is not kind or not layer.can_split():
                 raise NotImplementedError(f"kvcache_factory_amd: GraphDecoder found a {type(layer).__name__} in the cache after the "
                                           "prefill; graph-replayed decoding covers the plain compressed cache only")
-        if clusters is None:
+        if quant:                                                            # two words per layer: [0] tail rows, [1] residual rows
+            self._counter = torch.zeros(2, len(layers), dtype=torch.int32, device=dev)
+            self._stepped = self._counter[1]                                 # one vector for the in-graph add
+            cfg = self.config
+            layers = tuple(QuantizedDeviceLayer.adopt(layer, self.nbits, self.q_group_size, self.residual_length, self.tail_rows,
+                                                      self._counter[0, i:i + 1], self._counter[1, i:i + 1], cfg.num_key_value_heads)
+                           for i, layer in enumerate(layers))
+            cache.layers[:] = layers
+        elif clusters is None:
             self._counter = torch.zeros(1, dtype=torch.int32, device=dev)
             for layer in layers:
                 layer.enter_device_length(self._counter, self.tail_rows, self.config.num_key_value_heads)
@@ -207,6 +253,8 @@ class GraphDecoder:
             layers = tuple(twin.adopt(layer, cl, period, self._counter[i:i + 1], self.config.num_key_value_heads)
                            for i, (layer, cl) in enumerate(zip(layers, clusters)))
             cache.layers[:] = layers
+        if not quant:
+            self._stepped = self._counter                                    # what a step advances: every word
         self._cache, self._layers = cache, layers
         self._tok = torch.zeros(bsz, 1, dtype=torch.long, device=dev)
         self._pos = pos.contiguous()
@@ -220,7 +268,7 @@ class GraphDecoder:
         """The step every variant runs: model over the static buffers, logits to the static buffer, counter and positions on."""
         out = self.model(input_ids=self._tok, position_ids=self._pos, past_key_values=self._cache, use_cache=True)
         self._logits.copy_(out.logits)
-        self._counter.add_(1)
+        self._stepped.add_(1)
         self._pos.add_(1)
 
     def _capture(self):
@@ -233,7 +281,7 @@ class GraphDecoder:
             kept = [layer.scores_state() for layer in self._layers] if self.heavy_hitter is not None else ()
             for _ in range(self.WARMUP):
                 self._body()
-                self._counter.sub_(1)
+                self._stepped.sub_(1)
                 self._pos.sub_(1)
             for layer, state in zip(self._layers, kept):                     # (heavy_hitter: a warm-up step also added to the scores)
                 layer.set_scores_state(state)
@@ -256,7 +304,7 @@ class GraphDecoder:
         """tokens [bsz, 1] (device) -> the static logits buffer [bsz, 1, vocab].  No host read; a graph replay when capture=True."""
         if self._cache is None:
             raise RuntimeError("kvcache_factory_amd: GraphDecoder.step before prefill")
-        if self.interval is None and self.heavy_hitter is None:
+        if self.interval is None and self.heavy_hitter is None and self.nbits is None:
             for _ in range(tails_needed(self._capacity, self._tail, 1)):
                 self._grow()
         self._tok.copy_(tokens.reshape(self._tok.shape))
@@ -269,7 +317,13 @@ class GraphDecoder:
         self._tail += 1
         for layer in self._layers:                                           # the mirrors follow (no Python of the layers ran)
             layer.advance(1)
-        if self.interval is not None:
+        if self.nbits is not None:
+            grew = [layer.maybe_flush()[1] for layer in self._layers]        # host arithmetic; a flush is enqueued eagerly
+            if any(grew):                                                    # (every layer at once: they share R and the schedule)
+                self._capacity = self._layers[0].tail_capacity()
+                self._graph = None
+                self.grows += 1
+        elif self.interval is not None:
             for layer in self._layers:                                       # host arithmetic; a compression is enqueued eagerly
                 layer.maybe_compress()
         elif self.heavy_hitter is not None:
